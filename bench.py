@@ -1,18 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark: het-SNP allele calls/s + phased variants/s of the read-backed phasing hot path, whole-genome RNA-seq shape.
 
-python bench.py --gpus N --steps K --warmup W       (N>1: launched by torch.distributed.run, one rank per GPU)
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]       (N>1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps, writes the call lists of the last step when --dump-outputs is given, and prints the line (`value`,
+`ms_per_step`).  --full adds everything else: the re-checks of the call lists, the text-plane series and the roofline, the phasing pass, the CPU baselines,
+the configs[1] entry, the from-files entries and the RCCL self-check.
 
 Workload = BASELINE.json configs[2]: one GTEx-shape sample over the 22 autosomes, ~80M records of 76 bp and
 ~1.5M het SNPs distributed in proportion to chromosome length, packed as structure-of-arrays shards resident in HBM.
   * step (the K timed steps, `value`): K_map over every chromosome shard this rank owns, submitted as one batch
     (phz_map_reads_batch: the reference's pool.map over chromosomes, phaser.py:533) -> allele calls/s.
-  * phasing pass (`phasing.value`): stages T1-O2 on the same call lists -- AS cutoff (histogram + all-reduce), K_tally, noise
+  * phasing pass (`phasing.value`, --full): stages T1-O2 on the same call lists -- AS cutoff (histogram + all-reduce), K_tally, noise
     all-reduce, pair tests, components, block phasing, the rows of the five files, gather to rank 0 -> phased variants/s.
 With N GPUs the SAME 22 chromosomes are LPT-assigned to ranks by record count (strong scaling); both regions are bracketed by a
 barrier + synchronize on every rank and the max over ranks is reported.
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -28,6 +33,55 @@ import torch.distributed as dist
 
 HBM_PEAK_GBS = 8000.0     # MI355X spec (MI355X_MICROARCH.md); measured copy peak is ~6290 GB/s
 CALL_BYTES = 9            # read_idx 4 + var_idx 4 + code 1: the call list the phasing stage reads (the two planes behind the mapper drop-in's allele TEXT, 8 B more, are timed apart)
+
+
+DUMP_SAMPLE = 1 << 20     # calls per plane written by --dump-outputs (a seeded sample of them when the step made more)
+
+
+def dump_calls(out_dir, planes, seed=0):
+    """--dump-outputs: the call lists the timed step handed back in its last step, `planes` = [(read_idx, var_idx, code)] per shard in shard order, as
+    float64 .npy files in out_dir (about 32 MB, whatever the workload):
+      read_idx / var_idx / code  the shards' lists concatenated, at the positions call_index names: all of them up to DUMP_SAMPLE calls, beyond that a sample
+                                 drawn with a fixed seed (the same positions in every run that made the same number of calls);
+      calls_per_shard            the length of every shard's list;
+      calls_sum_per_shard        per shard the sums of read_idx, var_idx and code over ALL its calls (int64 sums, exact in float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = [int(p[0].numel()) for p in planes]
+    total = sum(counts)
+    sums = [[float(p[k].to(torch.int64).sum()) if counts[i] else 0.0 for k in range(3)] for i, p in enumerate(planes)]
+    if total > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).choice(total, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(total)
+    for k, name in enumerate(("read_idx", "var_idx", "code")):
+        cat = torch.cat([p[k].to(torch.int64) for p in planes]) if total else torch.zeros(0, dtype=torch.int64)
+        np.save(os.path.join(out_dir, name + ".npy"), cat[torch.from_numpy(idx).to(cat.device)].cpu().numpy().astype(np.float64))
+        del cat
+    np.save(os.path.join(out_dir, "call_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "calls_per_shard.npy"), np.asarray(counts, dtype=np.float64))
+    np.save(os.path.join(out_dir, "calls_sum_per_shard.npy"), np.asarray(sums, dtype=np.float64).reshape(len(planes), 3))
+
+
+@contextlib.contextmanager
+def reproducible_gene_draw():
+    """The workload generator (synth.make_read_plan) places read pairs on genes with torch.multinomial.  On the GPU that draw is not reproducible
+    for the ~12,000 genes of chr1 and chr2: about one call in ten returns a different draw (a few hundred of 20 M samples), so two runs would map
+    different reads.  torch's deterministic mode makes it reproducible; this turns that mode on around torch.multinomial alone while the
+    workload is generated, and leaves every other op as it is."""
+    orig = torch.multinomial
+
+    def multinomial(*args, **kw):
+        prev = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(True)
+        try:
+            return orig(*args, **kw)
+        finally:
+            torch.use_deterministic_algorithms(prev)
+    torch.multinomial = multinomial
+    try:
+        yield
+    finally:
+        torch.multinomial = orig
 
 
 def file_sha(*paths):
@@ -368,8 +422,14 @@ def self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)      # 0.3 s of timed steps by default (twenty 1.5 ms steps were a fragile headline)
+    # 200 steps = 0.3 s of timed steps by default (twenty 1.5 ms steps were a fragile headline); --from-files: 5 steps of ~0.3 s by default
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the re-checks of the call lists, the text-plane series and the roofline, the phasing pass, "
+                         "the CPU baselines, the configs[1] entry, the from-files entries and the RCCL self-check (the --no-* switches below prune this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the call lists of the last step to DIR/*.npy (float64; a seeded sample of 2^20 calls, see dump_calls)")
     ap.add_argument("--records", type=int, default=80_000_000)
     ap.add_argument("--snps", type=int, default=1_500_000)
     ap.add_argument("--baseq", type=int, default=10)
@@ -380,6 +440,10 @@ def main():
     ap.add_argument("--no-c2", action="store_true", help="skip the secondary configs[1] entry (chr1, 50M records, 40k het SNPs)")
     ap.add_argument("--no-bam", action="store_true", help="skip the from-files entries (a whole-genome BAM + VCF written to /tmp: bam_path = decoded on the GPU and on the host, end_to_end_files = the CLI on them)")
     a = ap.parse_args()
+    if a.steps is None:
+        a.steps = 5 if a.from_files else 200
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` by itself (no launcher): start N ranks of this script, one per GPU, under torch.distributed.run and let them
     # print the line (the reference's fan-out, phaser.py:2077-2094, is one Pool worker per chromosome; here one process per GPU)
@@ -428,14 +492,15 @@ def main():
     plan = workloads.genome_plan(a.records, a.snps)
     owner = pdist.assign_chromosomes({p[0]: float(p[3]) for p in plan}, world)       # LPT by record count
     mine = [p for p in plan if owner[p[0]] == rank]
-    want_cpu = rank == 0 and world == 1 and not a.no_cpu
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu
     t_gen = time.perf_counter()
     vsets = {}; shards = {}; sample = None
-    for chrom, ln, n_snps, n_rec, seed in mine:
-        v, shard, smp = workloads.make_shard(chrom, ln, n_snps, n_rec, seed, dev, keep_sample=n_rec if (want_cpu and chrom == "chr1") else 0)
-        vsets[chrom] = v; shards[chrom] = shard
-        if smp is not None:
-            sample = smp
+    with reproducible_gene_draw():
+        for chrom, ln, n_snps, n_rec, seed in mine:
+            v, shard, smp = workloads.make_shard(chrom, ln, n_snps, n_rec, seed, dev, keep_sample=n_rec if (want_cpu and chrom == "chr1") else 0)
+            vsets[chrom] = v; shards[chrom] = shard
+            if smp is not None:
+                sample = smp
     torch.cuda.synchronize()
     t_gen = time.perf_counter() - t_gen
     mapper = Mapper(local)
@@ -475,29 +540,35 @@ def main():
     per_step = sorted((stamps[i + 1] - stamps[i]) * 1e3 for i in range(a.steps))
     _, k_total_ms, k_n = mapper.ctx.timing(_lib.PHZ_T_MAP)
     assert [int(N[i]) for i in range(len(chroms))] == n_calls
+    if a.dump_outputs:
+        dump_calls(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, "rank%d" % rank),
+                   [[b[:n_calls[i]] for b in bufs[i][:3]] for i in range(len(chroms))])
 
-    # idempotence + mapper order (sortedness) on every shard at full size
-    for i, c in enumerate(chroms):
-        m = n_calls[i]
-        f = first[i]
-        assert all(bool(torch.equal(b[:m], t)) for b, t in zip(bufs[i][:3], (f.read_idx, f.var_idx, f.code))), "repeated passes differ"
-        key = bufs[i][0][:m].to(torch.int64) * (len(vsets[c]) + 1) + bufs[i][1][:m].to(torch.int64)
-        assert bool((key[1:] > key[:-1]).all()), "call list not in mapper order"
+    ms_with_text = None
+    alg_loc = {"stream_bytes": 0.0, "qual_lines": 0.0, "seq_lines": 0.0}
+    if a.full:
+        # idempotence + mapper order (sortedness) on every shard at full size
+        for i, c in enumerate(chroms):
+            m = n_calls[i]
+            f = first[i]
+            assert all(bool(torch.equal(b[:m], t)) for b, t in zip(bufs[i][:3], (f.read_idx, f.var_idx, f.code))), "repeated passes differ"
+            key = bufs[i][0][:m].to(torch.int64) * (len(vsets[c]) + 1) + bufs[i][1][:m].to(torch.int64)
+            assert bool((key[1:] > key[:-1]).all()), "call list not in mapper order"
 
-    # the same submission with the text planes (what the mapper drop-in asks for): a short series, reported next to the headline
-    call5, bufs5, N5 = mapper.prepare_batch(sh_list, vp_list, a.baseq, [n + 16 for n in n_calls], aux=True)
-    for _ in range(2):
-        mapper.ctx.check(call5())
-    torch.cuda.synchronize(); t5 = time.perf_counter()
-    for _ in range(max(1, min(a.steps, 20))):
-        mapper.ctx.check(call5())
-    torch.cuda.synchronize(); ms_with_text = (time.perf_counter() - t5) / max(1, min(a.steps, 20)) * 1e3
-    for i in range(len(chroms)):
-        m = n_calls[i]; f = first[i]
-        assert all(bool(torch.equal(b[:m], t)) for b, t in zip(bufs5[i], (f.read_idx, f.var_idx, f.code, f.aux0, f.aux1))), "text planes differ between passes"
-        assert all(bool(torch.equal(bufs5[i][k][:m], bufs[i][k][:m])) for k in range(3)), "call list differs with / without the text planes"
-    alg_loc = algorithmic_minimum(sh_list, vp_list, bufs5, n_calls)
-    del call5, bufs5
+        # the same submission with the text planes (what the mapper drop-in asks for): a short series, reported next to the headline
+        call5, bufs5, N5 = mapper.prepare_batch(sh_list, vp_list, a.baseq, [n + 16 for n in n_calls], aux=True)
+        for _ in range(2):
+            mapper.ctx.check(call5())
+        torch.cuda.synchronize(); t5 = time.perf_counter()
+        for _ in range(max(1, min(a.steps, 20))):
+            mapper.ctx.check(call5())
+        torch.cuda.synchronize(); ms_with_text = (time.perf_counter() - t5) / max(1, min(a.steps, 20)) * 1e3
+        for i in range(len(chroms)):
+            m = n_calls[i]; f = first[i]
+            assert all(bool(torch.equal(b[:m], t)) for b, t in zip(bufs5[i], (f.read_idx, f.var_idx, f.code, f.aux0, f.aux1))), "text planes differ between passes"
+            assert all(bool(torch.equal(bufs5[i][k][:m], bufs[i][k][:m])) for k in range(3)), "call list differs with / without the text planes"
+        alg_loc = algorithmic_minimum(sh_list, vp_list, bufs5, n_calls)
+        del call5, bufs5
     loc_calls = float(sum(n_calls)); loc_recs = float(sum(s.n for s in sh_list)); loc_snps = float(sum(len(vsets[c]) for c in chroms))
     red = torch.tensor([loc_calls, loc_recs, loc_snps, alg_loc["stream_bytes"], k_total_ms, float(k_n), 1.0, alg_loc["qual_lines"], alg_loc["seq_lines"]],
                        device=red_dev, dtype=torch.float64)
@@ -512,7 +583,7 @@ def main():
     # ---- second rate of the metric: phased variants/s over stages T1-O2 on the same call lists
     phasing = None
     gc.enable()
-    if not a.no_phasing:
+    if a.full and not a.no_phasing:
         vs = pvcf.load_variants("\n".join(synth.vcf_lines([workloads_variants(plan, vsets, p) for p in plan])))
         # host threads of the row writer: four per CPU the container may really use (quota-aware; the phases are short and bursty), shared by the ranks of the node
         host_threads = max(1, min(64, 4 * pdist.effective_cpus() // max(1, world)))
@@ -603,17 +674,18 @@ def main():
                        "step": "K_map over all chromosome shards of the rank in one batched submission (phz_map_reads_batch); call list = (record, variant, allele "
                                "code) per call, the form the phasing stage reads (SURVEY.md 8(a) M1)",
                        "step_ms_spread": {"min": per_step[0], "median": per_step[len(per_step) // 2], "p90": per_step[min(len(per_step) - 1, int(0.9 * len(per_step)))],
-                                          "max": per_step[-1], "note": "wall time of the individual timed steps on rank 0 (ms_per_step is their mean incl. the closing barrier)"},
-                       "step_with_text_planes_ms": ms_with_text,
-                       "step_with_text_planes_note": "the same submission also writing the two planes behind the mapper drop-in's allele text (read offset, inserted bases: "
-                                                     "8 more bytes per call), rank 0's shards, mean of a short series"},
-            "full_output_step": {"ms_per_step": ms_with_text, "value": tot_calls / (ms_with_text / 1e3) if world == 1 else None, "unit": "allele calls/s",
-                                 "bytes_per_call": 17,
-                                 "note": "the same submission writing all five planes of a call (record, variant, code + read offset of the base + inserted-bases word), what the mapper "
-                                         "drop-in (read_variant_map.do_read_variant_map) needs to print the allele text; rounds 1-3 reported THIS form as the headline, since "
-                                         "round 4 `value` is the 9-byte form the phasing stage reads"},
-            "roofline": kmap_roofline(mapper.ctx, tot_recs, alg, k_avg_s, k_launches, a.steps, k_ms_max_rank, world),
+                                          "max": per_step[-1], "note": "wall time of the individual timed steps on rank 0 (ms_per_step is their mean incl. the closing barrier)"}},
         }
+        if a.full:
+            out["config"]["step_with_text_planes_ms"] = ms_with_text
+            out["config"]["step_with_text_planes_note"] = ("the same submission also writing the two planes behind the mapper drop-in's allele text (read offset, "
+                                                           "inserted bases: 8 more bytes per call), rank 0's shards, mean of a short series")
+            out["full_output_step"] = {"ms_per_step": ms_with_text, "value": tot_calls / (ms_with_text / 1e3) if world == 1 else None, "unit": "allele calls/s",
+                                       "bytes_per_call": 17,
+                                       "note": "the same submission writing all five planes of a call (record, variant, code + read offset of the base + inserted-bases word), what "
+                                               "the mapper drop-in (read_variant_map.do_read_variant_map) needs to print the allele text; rounds 1-3 reported THIS form as the "
+                                               "headline, since round 4 `value` is the 9-byte form the phasing stage reads"}
+            out["roofline"] = kmap_roofline(mapper.ctx, tot_recs, alg, k_avg_s, k_launches, a.steps, k_ms_max_rank, world)
         if phasing is not None:
             out["phasing"] = phasing
             out["end_to_end"] = {"seconds": dt / a.steps + phasing["seconds_per_pass"], "unit": "s per sample, shards resident in HBM -> rows of the five files on rank 0",
@@ -639,14 +711,14 @@ def main():
                 calls_of = {c: Calls(*[None if t is None else t[:n_calls[i]] for t in bufs[i]]) for i, c in enumerate(chroms)}
                 phasing["cpu_baseline"] = cpu_phasing_baseline(["chr21", "chr22"], vsets, shards, calls_of, mapper, a.baseq,
                                                                all_cores_chroms=["chr%d" % i for i in range(15, 23)])
-        if world == 1 and not a.no_c2:
+        if a.full and world == 1 and not a.no_c2:
             out["secondary"] = configs1_entry(mapper, a, dev)
-        if world == 1 and not a.no_bam:
+        if a.full and world == 1 and not a.no_bam:
             try:
                 out["bam_path"], out["end_to_end_files"] = files_entries(mapper, dev, a)
             except Exception as e:                      # a side entry must never cost the bench line
                 out["bam_path"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and backend == "nccl":
+        if a.full and world == 1 and backend == "nccl":
             out["collective"]["rccl_selfcheck"] = rccl_selfcheck(local)
             out["collective"]["rccl_ranks"] = int(out["collective"]["rccl_selfcheck"].get("rccl_ranks", 0))
         print(json.dumps(out))
@@ -677,7 +749,8 @@ def write_genome_files(tmp, a, dev):
     for i, (chrom, ln) in enumerate(items):
         n_snps = int(a.snps * ln / total_len); n_pairs = int(40_000_000 * frac * ln / total_len)
         v, gs, ge, w = synth.make_variants(chrom, 1, ln, n_snps, 777 + i, n_genes=max(1, n_snps // 10))
-        plan = synth.make_read_plan(v, gs, ge, w, n_pairs, 1777 + i, device=dev)
+        with reproducible_gene_draw():
+            plan = synth.make_read_plan(v, gs, ge, w, n_pairs, 1777 + i, device=dev)
         for lo in range(0, len(plan), 2_000_000):
             rb = synth.fill_reads(plan, lo, min(len(plan), lo + 2_000_000), v, qname_prefix="s0.b0.%d." % i)
             batches.append(synth.ReadBatch(rb.chrom, rb.L, rb.pos.cpu(), rb.flag.cpu(), rb.mapq.cpu(), rb.tlen.cpu(), rb.aln_score.cpu(), rb.qid.cpu(),
@@ -730,10 +803,13 @@ def from_files_mode(a, rank, world, local, dev, red_dev, backend, dev_names):
             if sh is None:
                 raise RuntimeError("the device BAM path declined the file")
             calls = mapper.map_batch([sh[c] for c in mine if c in sh], [vpos[c] for c in mine if c in sh], a.baseq, aux=False) if sh else []
+            if a.dump_outputs:
+                last[:] = calls           # the lists of the last step, for dump_calls
             return sum(c.n for c in calls), sum(s_.n for s_ in sh.values())
+        last = []
         for _ in range(max(1, min(a.warmup, 2))):
             step()
-        steps = a.steps if a.steps != 200 else 5          # the default of the resident mode (200 steps of 1.3 ms) would be 200 x 0.4 s here
+        steps = a.steps
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -743,6 +819,8 @@ def from_files_mode(a, rank, world, local, dev, red_dev, backend, dev_names):
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
+        if a.dump_outputs:
+            dump_calls(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, "rank%d" % rank), [(c.read_idx, c.var_idx, c.code) for c in last])
         red = torch.tensor([float(n_calls), float(n_kept), 1.0, float(sum(w.get(c, 0) for c in mine))], device=red_dev, dtype=torch.float64)
         tmax = torch.tensor([dt], device=red_dev, dtype=torch.float64)
         if world > 1:

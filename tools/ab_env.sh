@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 : > $OUT/ab.txt
 for setting in "" "$@"; do
-  env $setting timeout 600 python bench.py --no-cpu --no-c2 --no-bam --steps 100 > /tmp/ab.out 2> /tmp/ab.err
+  env $setting timeout 600 python bench.py --full --no-cpu --no-c2 --no-bam --steps 100 > /tmp/ab.out 2> /tmp/ab.err
   python - "$setting" <<'P' >> $OUT/ab.txt
 import json, sys
 line = [l for l in open('/tmp/ab.out') if l.startswith('{')]

@@ -8,9 +8,9 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "p
 tools/prof_pmc_c3.sh $TAG > $OUT/pmc_kmap.log 2>&1; grep "k_map" $OUT/pmc_kmap.log | cut -c1-300
 tools/prof_pmc_tally.sh $TAG > $OUT/pmc_tally.log 2>&1; tail -3 $OUT/pmc_tally.log
 cd $R
-timeout 900 python bench.py > $OUT/bench.out 2> $OUT/bench.err; echo "bench rc=$?"; grep "^{" $OUT/bench.out | tail -1 > $OUT/bench.json; tail -2 $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.out 2> $OUT/bench.err; echo "bench rc=$?"; grep "^{" $OUT/bench.out | tail -1 > $OUT/bench.json; tail -2 $OUT/bench.err
 cd /tmp; rm -rf /tmp/pb
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o p -- python $R/bench.py --no-cpu --no-c2 > /tmp/pb.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o p -- python $R/bench.py --full --no-cpu --no-c2 > /tmp/pb.log 2>&1
 grep "^{" /tmp/pb.log | tail -1 > $OUT/bench_rocprof.json
 f=$(find /tmp/pb -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats.csv
 cd $R

@@ -4,7 +4,7 @@
 set -u
 R=$PWD; mkdir -p $R/gpurun_out
 export TMPDIR=/tmp; cd /tmp; rm -rf /tmp/pb
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o p -- python $R/bench.py > /tmp/pb.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o p -- python $R/bench.py --full > /tmp/pb.log 2>&1
 grep "^{" /tmp/pb.log | tail -1 > $R/gpurun_out/$1.json
 f=$(find /tmp/pb -name "*kernel_stats.csv" | head -1)
 cp $f $R/gpurun_out/$1_kernel_stats.csv

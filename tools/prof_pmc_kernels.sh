@@ -5,7 +5,7 @@ set -u
 R=$PWD; tag=$1; shift
 export TMPDIR=/tmp; cd /tmp
 rm -rf /tmp/pmck
-timeout 900 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d /tmp/pmck -o p -- python $R/bench.py --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmck.log 2>&1
+timeout 900 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d /tmp/pmck -o p -- python $R/bench.py --full --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmck.log 2>&1
 f=$(find /tmp/pmck -name "*counter_collection.csv" | head -1)
 mkdir -p $R/gpurun_out
 python - "$f" "$@" > $R/gpurun_out/${tag}_pmc_kernels.txt <<'PY'

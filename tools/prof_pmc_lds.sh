@@ -3,7 +3,7 @@
 set -u
 R=$PWD; tag=$1
 export TMPDIR=/tmp; cd /tmp; rm -rf /tmp/pmcl
-timeout 900 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d /tmp/pmcl -o p -- python $R/bench.py --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmcl.log 2>&1
+timeout 900 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d /tmp/pmcl -o p -- python $R/bench.py --full --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmcl.log 2>&1
 f=$(find /tmp/pmcl -name "*counter_collection.csv" | head -1)
 if [ -z "$f" ]; then tail -5 /tmp/pmcl.log; exit 1; fi
 python - "$f" > $R/gpurun_out/${tag}_pmc_lds.txt <<'PY'

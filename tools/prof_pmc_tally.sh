@@ -10,7 +10,7 @@ R=$PWD; OUT=$R/gpurun_out/$1/pmc_ktally_c3; mkdir -p $OUT
 export TMPDIR=/tmp; cd /tmp
 run() { name=$1; shift
   rm -rf /tmp/pmct_$name
-  timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmct_$name -o p -- python $R/bench.py --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmct_$name.log 2>&1
+  timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmct_$name -o p -- python $R/bench.py --full --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/pmct_$name.log 2>&1
   f=$(find /tmp/pmct_$name -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then python - "$f" $OUT/$name.csv <<'PY'
 import csv, sys
@@ -51,7 +51,7 @@ for name in ("fetch", "write"):
         tot[fam][name] = sum(float(r["Counter_Value"]) for r in rows if r["Family"] == fam)
     passes = max(passes, sum(1 for r in rows if r["Kernel_Name"].startswith("k_line")))
 json.dump({"workload": "configs[2]", "kernel_source_sha16": sha("phaser_amd/csrc/phz_tally.hip"), "rows_source_sha16": sha("phaser_amd/csrc/phz_rowsdev.hip"), "passes": passes,
-           "kib": tot, "command": "python bench.py --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1",
+           "kib": tot, "command": "python bench.py --full --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1",
            "units": "FETCH_SIZE / WRITE_SIZE in KiB summed over the family's dispatches of all passes; FETCH_SIZE must be doubled on gfx950 (MI355X_MICROARCH.md)"},
           open(os.path.join(out, "meta.json"), "w"), indent=1)
 for fam in tot:

@@ -3,7 +3,7 @@
 # dispatches of the kernels whose name contains $2, in stream order.  usage: tools/prof_trace.sh <tag> <kernel substring>
 R=${GRAFT_REPO_ROOT:-/root/repo}; tag=$1; pat=$2
 cd /tmp && export TMPDIR=/tmp; rm -rf /tmp/ptr
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/ptr -o p -- python $R/bench.py --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/ptr.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/ptr -o p -- python $R/bench.py --full --no-cpu --no-bam --no-c2 --steps 2 --warmup 1 --phasing-passes 1 > /tmp/ptr.log 2>&1
 f=$(find /tmp/ptr -name '*kernel_trace.csv' | head -1)
 python - "$f" "$pat" > $R/gpurun_out/${tag}_trace_${pat}.txt <<'PY'
 import csv, sys
