@@ -179,7 +179,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_COUNT = 8 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_COUNT = 9 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -394,6 +394,14 @@ int phz_sam_calls_tsv(const phz_sam *h, int shard, int64_t n_calls, const int32_
                       const uint32_t *aux0, const uint32_t *aux1, int baseq, const uint32_t *id_off, const char *id,
                       const uint32_t *rsid_off, const char *rsid, const uint32_t *gt_off, const char *gt, const uint32_t *maf_off,
                       const char *maf, int threads, char **out, int64_t *out_len);
+
+/* phaser_cis_var's VCF lookup (phaser_cis_var.py:276-284): the records of a bgzipped VCF at n_keys (contig, 1-based pos) keys, what tabix
+ * fetch(chr, pos-1, pos) + POS == pos return.  use_index and <path>.tbi present: only the index's BGZF chunks of those positions are inflated
+ * (merged spans, `threads` workers); otherwise the whole file.  *out: one line per record in file order, "key\tCHROM\tPOS\tID\tREF\tALT\tgt_index\t"
+ * + the GT subfield of each of the n_samples named samples (the last header column of that name; "\x01" where the header or the record lacks it;
+ * gt_index -1 when FORMAT has no GT).  *contigs_out: the VCF's contigs, one per line.  Both buffers are released with phz_buf_free. */
+int phz_vcf_lookup(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples, const char *const *samples,
+                   int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
 
 /* whole BGZF file -> buffer owned by the library (release it with phz_buf_free and nothing else: a large text is an anonymous mapping, not a malloc'd block);
  * PHZ_E_UNSUPPORTED when the file is plain gzip */
@@ -679,6 +687,30 @@ typedef struct {
 } phz_gene_work;
 
 int phz_gene_counts(phz_ctx *ctx, const phz_gene_work *work, int32_t *pair_counts, int space);
+
+/* K_boot: the bootstrap of phaser_cis_var (phaser_pop/phaser_cis_var.py:166-171, :202-219) for a batch of groups.  A group is the het or the hom
+ * sample set of one (pair row, VCF record); its n values in list order are values[off[g], off[g + 1]).  Draw j of replicate b is word (b*n + j) mod 4 of
+ * Philox4x32-10 with counter {lo(q), hi(q), lo(s), hi(s)}, q = (b*n + j) / 4, key {lo(seed), hi(seed)}, s = subseq[g] (rocrand_device::philox4x32_10_engine
+ * (seed, s, b*n + j)); the drawn sample is (word * n) >> 32.  Each replicate's median (numpy.median) is taken of the signed set (set 0) and of the |value|
+ * set (set 1) with the same draws.  rank[i] = rank of sample i among its group's signed values | rank among the |values| << 16; sorted_s / sorted_a
+ * hold each group's values in that rank order.  Per group and set, order_stats[8 g + 4 set + i] = the k[i]-th smallest replicate median (0-based,
+ * k[1] in {k[0], k[0] + 1}, k[3] in {k[2], k[2] + 1}) and sign_counts[4 g + 2 set + {0, 1}] = replicates > 0 / < 0.  replicates (optional, may be
+ * NULL): [g][set][bs] every replicate median.  Groups of up to 65535 samples; an empty group gets NaN order statistics and zero sign counts.
+ * PHZ_HOST inputs are checked; with PHZ_DEVICE the caller guarantees off nondecreasing from 0 and every group at most max_n samples (the
+ * scratch of large groups is sized by max_n). */
+typedef struct {
+    int64_t n_groups;
+    const int64_t *off;            /* [n_groups + 1] */
+    const uint64_t *subseq;        /* [n_groups] */
+    const uint32_t *rank;          /* [off[n_groups]] */
+    const double *sorted_s, *sorted_a;
+    int32_t max_n;                 /* largest group (sizes the scratch of groups that do not fit on chip) */
+    int32_t bs;
+    int32_t k[4];
+    uint64_t seed;
+} phz_boot_in;
+
+int phz_bootstrap_medians(phz_ctx *ctx, const phz_boot_in *in, double *order_stats, int64_t *sign_counts, double *replicates, int space);
 
 /* Output rows of phaser_gene_ae (:147-163), threaded.  Keys are bam * n_features + feature.  Pools: items followed by '\n'.
  * out is malloc'd (phz_buf_free). */

@@ -58,6 +58,7 @@ int phz_ctx_destroy(phz_ctx *c) {
     for (DevBuf &b : c->import_buf) free_buf(b);
     for (DevBuf &b : c->resident_vars) free_buf(b);
     free_buf(c->tally_qcount); free_buf(c->scan_state);
+    free_buf(c->boot_keys); free_buf(c->boot_hist);
     if (c->h_scalars.p) (void)hipHostFree(c->h_scalars.p);
     if (c->mail_host.p) (void)hipHostFree(c->mail_host.p);
     free_buf(c->mail_dev);

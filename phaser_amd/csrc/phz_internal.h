@@ -57,6 +57,7 @@ struct phz_ctx {
     DevBuf scan_state; uint32_t scan_epoch = 0, scan_ticket_base = 0;
     uint64_t tally_gen = 0;            // bumped by every phz_tally / phz_tally_import: stamps what later stages prepared for "the resident tally"
     uint64_t tally_table_cap = 0;      // slots of the variant-pair table that the last phz_tally needed
+    DevBuf boot_keys, boot_hist;       // K_boot: replicate medians per resident block, histograms of groups too large for LDS
     DevBuf tally_qcount;               // lines per QNAME: all zero between phz_tally calls (never shared with other stages)
     // results of the last phz_tally, resident in HBM until the next one (phz_tally_fetch / phz_components read them)
     struct {
