@@ -917,21 +917,6 @@ __global__ void k_block_counts(const uint32_t *start, const uint32_t *count, int
         blkvars[c] = blk_voff[b1] - blk_voff[b0]; cfgrows[c] = cfg_base[b1] - cfg_base[b0];
     }
 }
-// (few workgroups, one same-address atomic each: one per wave of 64 elements was 35 us for 186,000 blocks)
-__global__ __launch_bounds__(256) void k_max_u32(const uint32_t *x, int64_t n, unsigned long long *out) {
-    __shared__ uint32_t s_m[4];
-    uint32_t v = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) { const uint32_t y = x[i]; v = y > v ? y : v; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o > v ? o : v; }
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) v = s_m[w] > v ? s_m[w] : v;
-        if (v) atomicMax(out, (unsigned long long)v);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- block phasing (phase_v3)
 struct PH {
     const uint32_t *cstart, *mem_s, *estart, *ekeep, *eloc;
@@ -1823,7 +1808,9 @@ template <int MODE, int SLOTS, int THREADS, bool HUGE = false> __global__ __laun
 // seg_off[s] = off[sum of count[0..s)]: byte offsets of the per-chromosome (per BAM x chromosome) segments of a file
 // (one workgroup: every thread sums a contiguous chunk of the counts, the chunks' prefix comes from LDS -- one thread walking the segments with
 //  a dependent load each was 8 us per file)
-template <class C> __device__ __forceinline__ void seg_offsets_block(const C *count, unsigned long long mult, int nseg, const unsigned long long *off, unsigned long long *seg_off) {
+__global__ __launch_bounds__(256) void k_seg_offsets(const uint32_t *count, const uint32_t *mult_p, int nseg, const unsigned long long *off, unsigned long long *seg_off) {
+    if (blockIdx.x) return;
+    const unsigned long long mult = mult_p ? (unsigned long long)*mult_p : 1ull;
     __shared__ unsigned long long s_part[256];
     const int tid = threadIdx.x;
     const int chunk = (nseg + 1 + 255) / 256, beg = tid * chunk, end = beg + chunk < nseg + 1 ? beg + chunk : nseg + 1;
@@ -1834,14 +1821,6 @@ template <class C> __device__ __forceinline__ void seg_offsets_block(const C *co
     unsigned long long rows = 0;
     for (int t = 0; t < tid; t++) rows += s_part[t];
     for (int j = beg; j < end; j++) { seg_off[j] = off[rows]; if (j < nseg) rows += (unsigned long long)count[j] * mult; }
-}
-__global__ __launch_bounds__(256) void k_seg_offsets(const uint32_t *count, const uint32_t *mult, int nseg, const unsigned long long *off, unsigned long long *seg_off) {
-    if (blockIdx.x) return;
-    seg_offsets_block<uint32_t>(count, mult ? (unsigned long long)*mult : 1ull, nseg, off, seg_off);
-}
-__global__ __launch_bounds__(256) void k_seg_offsets64(const unsigned long long *count, int nseg, const unsigned long long *off, unsigned long long *seg_off) {
-    if (blockIdx.x) return;
-    seg_offsets_block<unsigned long long>(count, 1ull, nseg, off, seg_off);
 }
 __global__ __launch_bounds__(256) void k_count_nonzero(const uint32_t *len, int64_t n, unsigned long long *counter) {
     __shared__ unsigned int s_c[4];
@@ -1889,27 +1868,31 @@ __global__ __launch_bounds__(256) void k_vchrom(int64_t nv, const long long *chr
 }  // namespace
 
 // ================================================================================================ host side
+// Every device buffer of the handle, in ONE list: it declares the members of phz_rowsdev and it is what phz_rowsdev_destroy frees (B: one buffer, A: an array of them)
+#define PHZ_ROWSDEV_BUFS(B, A) \
+    /* static tables in HBM; pools: 0 uid, 1 rsid, 2 allele, 3 maf text, 4 chromosome names, 5 gwStat table */ \
+    B(d_chrom_v0) B(d_vchrom) B(d_pos) B(d_maf) B(d_isref) B(d_phase) B(d_black) A(p_off, 6) A(p_txt, 6) \
+    /* per pass; up_dev: the per-pass uploads (p-values and their text by slot, BAM names, shard line ranges) as pieces of one block; sh_dev: the first stage's shard table */ \
+    B(hkeys) B(flags) B(up_dev) B(sh_dev) B(keep) B(e_slot) B(deg) B(parent) B(label) B(f_a) B(f_b) B(f_c) B(f_d) B(mem_pos) B(cid) B(kpos) B(keypos) \
+    B(k64a) B(k64b) B(k32a) B(k32b) B(v32a) B(v32b) B(sort_cnt) B(scan_tmp) B(ridx) B(va) B(vb) B(eorder) B(mem_s) B(cstart) B(corder) B(ekeep) B(estart) B(key_g) \
+    B(cnt64) B(cnt32) B(chrom_cnt) B(seg_start) B(key64s) B(eloc) B(alle_of) B(sub_of) B(nsub) B(complex_list) B(exc_list) B(nsub_o) B(blk_base) \
+    B(blk_mstart) B(blk_len) B(blk_of) B(v_alle) B(blk_sup) B(blk_tot) B(conc) B(cormode) B(statkind) B(statidx) B(maxmaf) B(stat) B(cfg_rows) B(cfg_base) B(cfg_chunk) \
+    B(cfg_pl) B(cfg_pb) B(cfg_ps) B(cfg_bytes) B(cfg_bbase) B(blk_voff) B(mrec) B(lab_e) B(lab_skip) B(big_blk) B(labels) B(seg_ns) B(blk_cnt) B(single_n) B(big_list) B(big_list2) \
+    B(huge_list) B(big_stat) B(px_off) B(px_txt) B(pool) B(its) B(piece_dst) B(rowlen) A(off, PHZ_TXT_COUNT) A(seg_off_d, PHZ_TXT_COUNT) A(text, PHZ_TXT_COUNT) \
+    B(o_var) B(o_maxmaf) B(o_hap) B(o_cor) \
+    /* --output_read_ids 1 */ \
+    B(qn_off) B(qn_txt) B(qn_base) B(isf0) B(isf2)
+#define PHZ_BUF_DECL(name) DevBuf name;
+#define PHZ_BUF_DECL_ARRAY(name, n) DevBuf name[n];
+#define PHZ_BUF_VISIT(name) f(name);
+#define PHZ_BUF_VISIT_ARRAY(name, n) for (DevBuf &b_ : name) f(b_);
 struct phz_rowsdev {
     int64_t nv = 0;
     int nchrom = 0;
     bool has_black = false;
     std::vector<long long> chrom_v0;
-    // static tables in HBM
-    DevBuf d_chrom_v0, d_vchrom, d_pos, d_maf, d_isref, d_phase, d_black;
-    DevBuf p_off[6], p_txt[6];          // pools: 0 uid, 1 rsid, 2 allele, 3 maf text, 4 chromosome names, 5 gwStat table
-    // per pass
-    DevBuf hkeys, flags, up_dev;        // up_dev: the per-pass uploads (p-values and their text by slot, BAM names, shard line ranges) as pieces of one block
-    DevBuf up_host;                      // ... and its page-locked host image
-    DevBuf keep, e_slot, deg, parent, label, f_a, f_b, f_c, f_d, mem_pos, cid, kpos, keypos;
-    DevBuf k64a, k64b, k32a, k32b, v32a, v32b, sort_cnt, scan_tmp;
-    DevBuf ridx, va, vb, eorder, mem_s, cstart, corder, ekeep, estart, key_g;
-    DevBuf cnt64, cnt32, chrom_cnt, seg_start, key64s, eloc;     // chrom_cnt: uint32 [conn rows | blocks | block vars | keys per (bam, chrom)], then uint64 cfg rows
-    DevBuf alle_of, sub_of, nsub, complex_list, exc_list, nsub_o, blk_base;
-    DevBuf blk_mstart, blk_len, blk_of, v_alle, blk_sup, blk_tot, conc, cormode, statkind, statidx, maxmaf, stat, cfg_rows, cfg_base, cfg_chunk, cfg_pl, cfg_pb, cfg_ps, cfg_bytes, cfg_bbase, blk_voff, mrec, lab_e, lab_skip, big_blk;
-    DevBuf labels, seg_ns, blk_cnt, single_n, big_list, big_list2, huge_list, big_stat, px_off, px_txt, pool, tl, its, piece_dst, rowlen;
-    DevBuf off[PHZ_TXT_COUNT], seg_off_d[PHZ_TXT_COUNT], text[PHZ_TXT_COUNT];
-    DevBuf o_var, o_maxmaf, o_hap, o_cor;
-    DevBuf qn_off, qn_txt, qn_base, isf0, isf2;      // --output_read_ids 1
+    PHZ_ROWSDEV_BUFS(PHZ_BUF_DECL, PHZ_BUF_DECL_ARRAY)
+    DevBuf up_host, sh_host;            // the page-locked host images of up_dev / sh_dev
     // results (host)
     int64_t bytes[PHZ_TXT_COUNT] = {0};
     std::vector<int64_t> seg_off[PHZ_TXT_COUNT];
@@ -1923,29 +1906,24 @@ struct phz_rowsdev {
     // covered variants compacted, sorted by (BAM, first line), their per-(BAM, chromosome) segment starts and counts -- all p-value-independent
     bool have_shards = false, pre_keys = false; int64_t pre_nkeys = 0;
     std::vector<long long> sh_lo, sh_hi; std::vector<int32_t> sh_bam;
-    DevBuf sh_dev, sh_host;
     hipEvent_t txt_ev[PHZ_TXT_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // "the writer of file f has finished" (copy-as-written)
     int64_t ps_slots = PS_SLOTS;        // slots of the pair-key hash set (a power of two; grown by the host when a pass reports PHZ_E_CAPACITY)
-    std::vector<DevBuf *> all() {
-        std::vector<DevBuf *> v = {&d_chrom_v0, &d_vchrom, &d_pos, &d_maf, &d_isref, &d_phase, &d_black, &hkeys, &flags, &up_dev, &keep, &e_slot, &deg, &parent, &label, &f_a, &f_b, &f_c, &f_d, &mem_pos, &cid, &kpos, &keypos,
-                                   &k64a, &k64b, &k32a, &k32b, &v32a, &v32b, &sort_cnt, &scan_tmp, &ridx, &va, &vb, &eorder, &mem_s, &cstart, &corder, &ekeep, &estart,
-                                   &key_g, &cnt64, &cnt32, &chrom_cnt, &seg_start, &key64s, &eloc, &alle_of, &sub_of, &nsub, &complex_list, &exc_list, &nsub_o, &blk_base, &blk_mstart, &blk_len,
-                                   &blk_of, &v_alle, &blk_sup, &blk_tot, &conc, &cormode, &statkind, &statidx, &maxmaf, &stat, &cfg_rows, &cfg_base, &cfg_chunk, &cfg_pl, &cfg_pb, &cfg_ps, &cfg_bytes, &cfg_bbase, &blk_voff, &mrec, &lab_e, &lab_skip, &big_blk, &labels,
-                                   &seg_ns, &blk_cnt, &single_n, &big_list, &big_list2, &huge_list, &big_stat, &px_off, &px_txt, &pool, &tl, &its, &piece_dst, &rowlen, &o_var, &o_maxmaf, &o_hap, &o_cor, &qn_off, &qn_txt, &qn_base, &isf0, &isf2, &sh_dev};
-        for (int i = 0; i < 6; i++) { v.push_back(&p_off[i]); v.push_back(&p_txt[i]); }
-        for (int i = 0; i < PHZ_TXT_COUNT; i++) { v.push_back(&off[i]); v.push_back(&seg_off_d[i]); v.push_back(&text[i]); }
-        return v;
-    }
+    template <class F> void each_buf(F f) { PHZ_ROWSDEV_BUFS(PHZ_BUF_VISIT, PHZ_BUF_VISIT_ARRAY) }
 };
 
 namespace {
-
 int up(phz_ctx *ctx, DevBuf &b, const void *src, size_t bytes) {
     if (int s = phz_reserve(ctx, b, bytes ? bytes : 1)) return s;
     if (bytes) PHZ_HIP(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return PHZ_OK;
 }
 template <class T> T *P(DevBuf &b) { return (T *)b.p; }
+// reserve a list of (buffer, bytes); the first failure ends it
+struct Rsv { DevBuf &b; size_t bytes; };
+int reserve_all(phz_ctx *ctx, std::initializer_list<Rsv> list) {
+    for (const Rsv &r : list) if (int s = phz_reserve(ctx, r.b, r.bytes)) return s;
+    return PHZ_OK;
+}
 
 // GPU time of the stage = sum over the sync-free sections between two host waits (the host work in between -- scipy, exceptions -- is not GPU time)
 struct Sections {
@@ -1974,6 +1952,40 @@ struct Sections {
     }
 };
 
+// bit widths of the fields of the sort keys: call lines of a BAM (line_real: without the tests' override), variants, BAMs
+struct KeyBits { int line, line_real, var, bam; };
+KeyBits key_bits(phz_ctx *ctx) {
+    auto &T = ctx->tally;
+    KeyBits k;
+    k.line = k.line_real = bits_for((uint64_t)(T.n_lines > 1 ? T.n_lines - 1 : 1));
+    if (const char *fb = getenv("PHZ_ROWS_FAKE_LINE_BITS")) k.line = std::max(k.line, std::min(32, atoi(fb)));      // tests: the key layout of a BAM with > 2^31 call lines
+    k.var = bits_for((uint64_t)(T.nv > 1 ? T.nv - 1 : 1)); k.bam = T.nb > 1 ? bits_for((uint64_t)(T.nb - 1)) : 0;
+    return k;
+}
+
+// layout of the per-chromosome counters / segment starts (chrom_cnt, seg_start): uint32 [conn rows | blocks | block vars | keys per (BAM, chromosome)], then (chrom_cnt only) uint64 cfg rows
+struct ChromTab { uint32_t *conn, *blocks, *blkvars, *keys; };
+struct ChromLayout {
+    int nchrom, nb;
+    size_t n32() const { return (size_t)nchrom * 3 + (size_t)nb * nchrom; }
+    size_t count_bytes() const { return n32() * 4 + 8 + (size_t)nchrom * 8; }          // chrom_cnt
+    size_t start_bytes() const { return (n32() + 1) * 4; }                              // seg_start: first row of every segment, same layout as the counters
+    ChromTab tab(void *base) const { uint32_t *p = (uint32_t *)base; return ChromTab{p, p + nchrom, p + 2 * (size_t)nchrom, p + 3 * (size_t)nchrom}; }
+    unsigned long long *cfg_rows(void *chrom_cnt) const { return (unsigned long long *)((char *)chrom_cnt + ((n32() * 4 + 7) & ~(size_t)7)); }
+};
+
+// The buffers BOTH stages touch -- the sort scratch, the ordering results, the key flags / positions, the per-chromosome tables -- sized from the resident tally alone.
+// What phz_rowsdev_pair_keys leaves in them must still be there when phz_rowsdev_run comes (phz_reserve frees and reallocates on growth): every user reserves them HERE.
+int reserve_shared(phz_ctx *ctx, phz_rowsdev *h) {
+    auto &T = ctx->tally;
+    const size_t NV = (size_t)(T.nv ? T.nv : 1), NE = (size_t)(T.n_edges ? T.n_edges : 1), NS = std::max(NV, NE);
+    const ChromLayout lay{h->nchrom, T.nb};
+    return reserve_all(ctx, {{h->k64a, NS * 8}, {h->k64b, NS * 8}, {h->k32a, NS * 4}, {h->k32b, NS * 4}, {h->v32a, NS * 4}, {h->v32b, NS * 4},
+                             {h->ridx, NV * 4}, {h->va, NE * 4}, {h->vb, NE * 4}, {h->eorder, NE * 4},
+                             {h->f_a, NS * 4}, {h->f_d, NV * 4}, {h->keypos, (NV + 1) * 4}, {h->cnt64, 64},
+                             {h->chrom_cnt, lay.count_bytes()}, {h->seg_start, lay.start_bytes()}});
+}
+
 // sort `n` (key, value) pairs living in (ka, va) with scratch (kb, vb); the sorted values land in `dst_val` (and the keys in dst_key if given): the last
 // pass of the one-launch-per-pass sort writes there directly
 template <class K>
@@ -1994,24 +2006,23 @@ int sort_into(phz_ctx *ctx, phz_rowsdev *h, DevBuf &ka, DevBuf &kb, int64_t n, c
 // phase_enqueue puts both kernels on the stream WITHOUT a host wait (k_phase_general takes its components in ticket order and reads their number on the
 // device); the caller reads cnt32[0..2] (complex components, exceptions, "cannot be split" flag) with its next wait and hands them to phase_exceptions.
 constexpr unsigned PH_GRID = 4096;     // waves of k_phase_general (a genome has ~20,000 complex components; each wave takes the next one until the list is empty)
-int phase_enqueue(phz_ctx *ctx, DevBuf &cstart, DevBuf &mem_s, DevBuf &estart, DevBuf &ekeep, const int32_t *ea, const int32_t *eb, const int32_t *cfgv,
-                  int64_t ncomp, int64_t nmem, int64_t nkeep, int max_block_size, DevBuf &alle_of, DevBuf &sub_of, DevBuf &nsub, DevBuf &complex_list,
-                  DevBuf &exc_list, DevBuf &eloc, uint32_t *cnt32) {
+struct PhaseArgs {
+    DevBuf &cstart, &mem_s, &estart, &ekeep; const int32_t *ea, *eb, *cfgv; int64_t ne, ncomp, nmem, nkeep; int max_block_size;      // the components and the pairs ekeep points into: given
+    DevBuf &alle_of, &sub_of, &nsub, &complex_list, &exc_list, &eloc; uint32_t *cnt32;                                             // results and work lists (reserved by phase_enqueue), counters
+};
+int phase_enqueue(phz_ctx *ctx, const PhaseArgs &a) {
     hipStream_t sm = ctx->stream;
-    if (int s = phz_reserve(ctx, alle_of, (size_t)(nmem + 1))) return s;
-    if (int s = phz_reserve(ctx, sub_of, (size_t)(nmem + 1) * 4)) return s;
-    if (int s = phz_reserve(ctx, nsub, (size_t)(ncomp + 1) * 4)) return s;
-    if (int s = phz_reserve(ctx, complex_list, (size_t)(ncomp + 1) * 4)) return s;
-    if (int s = phz_reserve(ctx, exc_list, (size_t)(2 * ncomp + 2) * 4)) return s;
-    if (int s = phz_reserve(ctx, eloc, (size_t)(nkeep + 1) * 4)) return s;
-    PHZ_HIP(ctx, hipMemsetAsync(cnt32, 0, 32, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(cnt32 + PH_TICKET, 0, 4, sm));
+    const int64_t ncomp = a.ncomp, nmem = a.nmem, nkeep = a.nkeep;
+    if (int s = reserve_all(ctx, {{a.alle_of, (size_t)(nmem + 1)}, {a.sub_of, (size_t)(nmem + 1) * 4}, {a.nsub, (size_t)(ncomp + 1) * 4}, {a.complex_list, (size_t)(ncomp + 1) * 4},
+                                  {a.exc_list, (size_t)(2 * ncomp + 2) * 4}, {a.eloc, (size_t)(nkeep + 1) * 4}})) return s;
+    PHZ_HIP(ctx, hipMemsetAsync(a.cnt32, 0, 32, sm));
+    PHZ_HIP(ctx, hipMemsetAsync(a.cnt32 + PH_TICKET, 0, 4, sm));
     if (!ncomp) return PHZ_OK;
-    PH ph; ph.cstart = P<uint32_t>(cstart); ph.mem_s = P<uint32_t>(mem_s); ph.estart = P<uint32_t>(estart); ph.ekeep = P<uint32_t>(ekeep);
-    ph.ea = ea; ph.eb = eb; ph.cfgv = cfgv; ph.alle_of = P<uint8_t>(alle_of); ph.sub_of = P<int32_t>(sub_of); ph.nsub = P<uint32_t>(nsub);
-    ph.complex_list = P<uint32_t>(complex_list); ph.exc_list = P<uint32_t>(exc_list); ph.counters = cnt32; ph.max_block_size = max_block_size;
-    ph.eloc = P<uint32_t>(eloc);
-    if (nkeep) hipLaunchKernelGGL(k_edge_local, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, ncomp, ph, P<uint32_t>(eloc));
+    PH ph; ph.cstart = P<uint32_t>(a.cstart); ph.mem_s = P<uint32_t>(a.mem_s); ph.estart = P<uint32_t>(a.estart); ph.ekeep = P<uint32_t>(a.ekeep);
+    ph.ea = a.ea; ph.eb = a.eb; ph.cfgv = a.cfgv; ph.alle_of = P<uint8_t>(a.alle_of); ph.sub_of = P<int32_t>(a.sub_of); ph.nsub = P<uint32_t>(a.nsub);
+    ph.complex_list = P<uint32_t>(a.complex_list); ph.exc_list = P<uint32_t>(a.exc_list); ph.counters = a.cnt32; ph.max_block_size = a.max_block_size;
+    ph.eloc = P<uint32_t>(a.eloc);
+    if (nkeep) hipLaunchKernelGGL(k_edge_local, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, ncomp, ph, P<uint32_t>(a.eloc));
     hipLaunchKernelGGL(k_phase_pair, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, ph);
     hipLaunchKernelGGL(k_phase_general, dim3((unsigned)std::min<int64_t>(ncomp, (int64_t)PH_GRID)), dim3(64), 0, sm, ph);
     PHZ_HIP(ctx, hipGetLastError());
@@ -2019,20 +2030,19 @@ int phase_enqueue(phz_ctx *ctx, DevBuf &cstart, DevBuf &mem_s, DevBuf &estart, D
 }
 // components beyond the kernel's limits (more than PH_NMAX variants / PH_EMAX pairs / a brute-force fragment of more than PH_BRUTE_MAX variants):
 // phase_v3 on the host (the same routine the host row stage runs), results written back.  h_c32 = cnt32[0..2] as read by the caller AFTER the kernels.
-int phase_exceptions(phz_ctx *ctx, const uint32_t *h_c32, DevBuf &cstart, DevBuf &mem_s, DevBuf &estart, DevBuf &ekeep, const int32_t *ea, const int32_t *eb, const int32_t *cfgv,
-                     int64_t ncomp, int64_t nmem, int64_t nkeep, int64_t ne, int max_block_size, DevBuf &alle_of, DevBuf &sub_of, DevBuf &nsub, DevBuf &exc_list) {
+int phase_exceptions(phz_ctx *ctx, const uint32_t *h_c32, const PhaseArgs &a) {
     if (h_c32[2]) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "a haplotype block cannot be split to --max_block_size (the reference does not terminate on it)");
     if (!h_c32[1]) return PHZ_OK;
-    std::vector<uint32_t> exc(h_c32[1]), cs((size_t)ncomp + 1), es((size_t)ncomp + 1), mem((size_t)nmem), ek((size_t)nkeep);
-    std::vector<int32_t> hea((size_t)ne), heb((size_t)ne), hcf((size_t)ne);
-    PHZ_HIP(ctx, hipMemcpy(exc.data(), exc_list.p, exc.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(cs.data(), cstart.p, cs.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(es.data(), estart.p, es.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(mem.data(), mem_s.p, mem.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(ek.data(), ekeep.p, ek.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(hea.data(), ea, hea.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(heb.data(), eb, heb.size() * 4, hipMemcpyDeviceToHost));
-    PHZ_HIP(ctx, hipMemcpy(hcf.data(), cfgv, hcf.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> exc(h_c32[1]), cs((size_t)a.ncomp + 1), es((size_t)a.ncomp + 1), mem((size_t)a.nmem), ek((size_t)a.nkeep);
+    std::vector<int32_t> hea((size_t)a.ne), heb((size_t)a.ne), hcf((size_t)a.ne);
+    PHZ_HIP(ctx, hipMemcpy(exc.data(), a.exc_list.p, exc.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(cs.data(), a.cstart.p, cs.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(es.data(), a.estart.p, es.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(mem.data(), a.mem_s.p, mem.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(ek.data(), a.ekeep.p, ek.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(hea.data(), a.ea, hea.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(heb.data(), a.eb, heb.size() * 4, hipMemcpyDeviceToHost));
+    PHZ_HIP(ctx, hipMemcpy(hcf.data(), a.cfgv, hcf.size() * 4, hipMemcpyDeviceToHost));
     std::sort(exc.begin(), exc.end());
     exc.erase(std::unique(exc.begin(), exc.end()), exc.end());
     for (uint32_t c : exc) {
@@ -2045,7 +2055,7 @@ int phase_exceptions(phz_ctx *ctx, const uint32_t *h_c32, DevBuf &cstart, DevBuf
             ec[t] = (int8_t)hcf[e];
         }
         int32_t nsubs = 0;
-        const int st = phz_phase_block((int32_t)n, (int64_t)E, ei.data(), ej.data(), ec.data(), max_block_size, sf.data(), sl.data(), cfg.data(), &nsubs);
+        const int st = phz_phase_block((int32_t)n, (int64_t)E, ei.data(), ej.data(), ec.data(), a.max_block_size, sf.data(), sl.data(), cfg.data(), &nsubs);
         if (st != PHZ_OK) return phz_fail(ctx, st, "block phasing of a large component on the host");
         std::vector<int32_t> so(n, -1); std::vector<uint8_t> ao(n, 0);
         uint32_t ns = 0; size_t w = 0;
@@ -2054,9 +2064,9 @@ int phase_exceptions(phz_ctx *ctx, const uint32_t *h_c32, DevBuf &cstart, DevBuf
             for (int32_t t = 0; t < sl[k]; t++) { so[(size_t)sf[k] + t] = (int32_t)ns; ao[(size_t)sf[k] + t] = (uint8_t)(cfg[w++] == '1'); }
             ns++;
         }
-        PHZ_HIP(ctx, hipMemcpy(P<int32_t>(sub_of) + m0, so.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        PHZ_HIP(ctx, hipMemcpy(P<uint8_t>(alle_of) + m0, ao.data(), (size_t)n, hipMemcpyHostToDevice));
-        PHZ_HIP(ctx, hipMemcpy(P<uint32_t>(nsub) + c, &ns, 4, hipMemcpyHostToDevice));
+        PHZ_HIP(ctx, hipMemcpy(P<int32_t>(a.sub_of) + m0, so.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        PHZ_HIP(ctx, hipMemcpy(P<uint8_t>(a.alle_of) + m0, ao.data(), (size_t)n, hipMemcpyHostToDevice));
+        PHZ_HIP(ctx, hipMemcpy(P<uint32_t>(a.nsub) + c, &ns, 4, hipMemcpyHostToDevice));
     }
     return PHZ_OK;
 }
@@ -2068,15 +2078,9 @@ int phase_exceptions(phz_ctx *ctx, const uint32_t *h_c32, DevBuf &cstart, DevBuf
 int order_variants_and_pairs(phz_ctx *ctx, phz_rowsdev *h, unsigned long long max_gap) {
     auto &T = ctx->tally;
     hipStream_t sm = ctx->stream;
-    const int64_t nv = T.nv, ne = T.n_edges, n_lines = T.n_lines;
-    const size_t NV = (size_t)(nv ? nv : 1), NE = (size_t)(ne ? ne : 1), NS = std::max(NV, NE);
-#define RSV(buf, bytes) do { if (int s_ = phz_reserve(ctx, h->buf, (bytes))) return s_; } while (0)
-    RSV(k64a, NS * 8); RSV(k64b, NS * 8); RSV(k32a, NS * 4); RSV(k32b, NS * 4); RSV(v32a, NS * 4); RSV(v32b, NS * 4);
-    RSV(ridx, NV * 4); RSV(va, NE * 4); RSV(vb, NE * 4); RSV(eorder, NE * 4);
-#undef RSV
-    const int bv = bits_for((uint64_t)(nv > 1 ? nv - 1 : 1));
-    int bl = bits_for((uint64_t)(n_lines > 1 ? n_lines - 1 : 1));
-    if (const char *fb = getenv("PHZ_ROWS_FAKE_LINE_BITS")) bl = std::max(bl, std::min(32, atoi(fb)));      // tests: the key layout of a BAM with > 2^31 call lines
+    const int64_t nv = T.nv, ne = T.n_edges;
+    if (int s = reserve_shared(ctx, h)) return s;
+    const KeyBits kb = key_bits(ctx); const int bv = kb.var, bl = kb.line;
     if (nv) {
         const int gb = bits_for((uint64_t)(max_gap ? max_gap : 1));
         const uint32_t *rank_order = P<uint32_t>(h->k32a);
@@ -2104,22 +2108,18 @@ int order_variants_and_pairs(phz_ctx *ctx, phz_rowsdev *h, unsigned long long ma
 
 // First-appearance keys (ordering rule 5 of SURVEY 8.1: allelic_counts and the singleton rows list the covered variants by the BAM and line of their first kept call):
 // compaction, sort by (BAM of the first line, line), segment starts per (BAM, chromosome) and their counts.  p-value-independent: enqueued by the first stage when the
-// handle knows the tally's shards, by phz_rowsdev_run otherwise.  ss_keys / cc_keys: the key segments of seg_start / chrom_cnt (cleared by the caller).
-int key_stage(phz_ctx *ctx, phz_rowsdev *h, int64_t nkeys, const long long *d_sh_lo, const long long *d_sh_hi, const int32_t *d_sh_bam, int n_shards, uint32_t *ss_keys, uint32_t *cc_keys) {
+// handle knows the tally's shards (ST: their device table), by phz_rowsdev_run otherwise.  The key segments of seg_start / chrom_cnt are cleared by the caller.
+int key_stage(phz_ctx *ctx, phz_rowsdev *h, int64_t nkeys, const ShardTab &ST) {
     auto &T = ctx->tally;
     hipStream_t sm = ctx->stream;
-    const int64_t nv = T.nv, n_lines = T.n_lines;
-    const int nb = T.nb, nchrom = h->nchrom;
-    const size_t NV = (size_t)(nv ? nv : 1), NE = (size_t)(T.n_edges ? T.n_edges : 1), NS = std::max(NV, NE);
-#define RSV(buf, bytes) do { if (int s_ = phz_reserve(ctx, h->buf, (bytes))) return s_; } while (0)
-    RSV(k64a, NS * 8); RSV(k64b, NS * 8); RSV(k32a, NS * 4); RSV(k32b, NS * 4); RSV(v32a, NS * 4); RSV(v32b, NS * 4);
-    RSV(key_g, (size_t)(nkeys + 1) * 4);
-    int bl = bits_for((uint64_t)(n_lines > 1 ? n_lines - 1 : 1));
-    if (const char *fb = getenv("PHZ_ROWS_FAKE_LINE_BITS")) bl = std::max(bl, std::min(32, atoi(fb)));      // tests: the key layout of a BAM with > 2^31 call lines
+    const int64_t nv = T.nv; const int nb = T.nb, nchrom = h->nchrom;
+    if (int s = reserve_shared(ctx, h)) return s;
+    if (int s = phz_reserve(ctx, h->key_g, (size_t)(nkeys + 1) * 4)) return s;
+    const ChromLayout lay{nchrom, nb};
+    uint32_t *ss_keys = lay.tab(h->seg_start.p).keys, *cc_keys = lay.tab(h->chrom_cnt.p).keys;
+    const KeyBits kb = key_bits(ctx); const int bl = kb.line, bb = kb.bam;
     if (nkeys) {
-        ShardTab ST; ST.lo = d_sh_lo; ST.hi = d_sh_hi; ST.bam = d_sh_bam; ST.n = n_shards;
-        const int bb = nb > 1 ? bits_for((uint64_t)(nb - 1)) : 0;
-        RSV(key64s, (size_t)(nkeys + 1) * 8);
+        if (int s = phz_reserve(ctx, h->key64s, (size_t)(nkeys + 1) * 8)) return s;
         if (bl < 32 && bb + bl <= 32 && getenv("PHZ_ROWS_SORT64") == nullptr) {        // (BAM, first line) in one 32-bit key; bl == 32 (one BAM of > 2^31 lines) would make the kernels shift a 32-bit word by 32
             hipLaunchKernelGGL(k_compact_keys32, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const long long *)T.var_first, (const uint32_t *)h->keypos.p, ST, bl,
                                P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
@@ -2130,20 +2130,27 @@ int key_stage(phz_ctx *ctx, phz_rowsdev *h, int64_t nkeys, const long long *d_sh
         } else {
             hipLaunchKernelGGL(k_compact_keys, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const long long *)T.var_first, (const uint32_t *)h->keypos.p, ST,
                                P<unsigned long long>(h->k64a), P<uint32_t>(h->v32a));
-            const int rg[2][2] = {{0, bits_for((uint64_t)(n_lines > 1 ? n_lines - 1 : 1))}, {32, 32 + (nb > 1 ? bits_for((uint64_t)(nb - 1)) : 0)}};
+            const int rg[2][2] = {{0, kb.line_real}, {32, 32 + bb}};
             if (int s = sort_into<unsigned long long>(ctx, h, h->k64a, h->k64b, nkeys, rg, 2, P<uint32_t>(h->key_g), P<unsigned long long>(h->key64s))) return s;
             hipLaunchKernelGGL(k_key_starts, dim3(nblk(nkeys)), dim3(256), 0, sm, nkeys, (const unsigned long long *)h->key64s.p, (const uint32_t *)h->key_g.p,
                                (const uint16_t *)h->d_vchrom.p, nchrom, ss_keys);
         }
     }
-#undef RSV
     hipLaunchKernelGGL(k_starts_to_counts, dim3(1), dim3(1), 0, sm, ss_keys, nb * nchrom, (uint32_t)nkeys, cc_keys);
     PHZ_HIP(ctx, hipGetLastError());
     return PHZ_OK;
 }
 
-// layout of the per-chromosome counters / segment starts (chrom_cnt, seg_start): uint32 [conn | blocks | block vars | keys per (BAM, chromosome)], then uint64 cfg rows per chromosome
-inline size_t n_chrom_counters(int nchrom, int nb) { return (size_t)nchrom * 3 + (size_t)nb * nchrom; }
+// The read-set kernels of one mode over the segments of sg: k_seg_small classifies the segments and counts the short lists, the wave / workgroup kernels take their
+// lists in ticket order.  Fixed numbers of workgroups for the list kernels: what a chip holds at once (10 KB / 52 KB of LDS each); a short list leaves most of them
+// with nothing but one ticket.  (Mode 2 has one piece per segment: never huge.)
+template <int MODE> void launch_read_sets(hipStream_t sm, const SG &sg) {
+    const unsigned g = (unsigned)((sg.nseg + 63) / 64), g_mid = (unsigned)std::min<int64_t>(sg.nseg, 4096), g_large = (unsigned)std::min<int64_t>(sg.nseg, 768);
+    hipLaunchKernelGGL(k_seg_small<MODE>, dim3(g), dim3(64), 0, sm, sg);
+    hipLaunchKernelGGL((k_seg_big<MODE, 512, 64>), dim3(g_mid), dim3(64), 0, sm, sg);
+    hipLaunchKernelGGL((k_seg_big<MODE, 4096, PHZ_SEG_THREADS>), dim3(g_large), dim3(PHZ_SEG_THREADS), 0, sm, sg);
+    if constexpr (MODE != 2) hipLaunchKernelGGL((k_seg_big<MODE, 4096, PHZ_SEG_THREADS, true>), dim3((unsigned)std::min<int64_t>(sg.nseg, 64)), dim3(PHZ_SEG_THREADS), 0, sm, sg);
+}
 
 }  // namespace
 
@@ -2202,7 +2209,7 @@ extern "C" int phz_rowsdev_create(phz_ctx *ctx, const phz_rowsdev_tables *t, phz
 
 extern "C" void phz_rowsdev_destroy(phz_rowsdev *h) {
     if (!h) return;
-    for (DevBuf *b : h->all()) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    h->each_buf([](DevBuf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; });
     if (h->up_host.p) (void)hipHostFree(h->up_host.p);
     if (h->sh_host.p) (void)hipHostFree(h->sh_host.p);
     for (hipEvent_t e : h->txt_ev) if (e) (void)hipEventDestroy(e);
@@ -2227,8 +2234,7 @@ extern "C" int phz_rowsdev_pair_keys(phz_ctx *ctx, phz_rowsdev *h, uint64_t *key
     if (T.nv != h->nv) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev: the resident tally does not belong to these variant tables");
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     const size_t slots = (size_t)h->ps_slots;
-    if (int s = phz_reserve(ctx, h->hkeys, slots * 8)) return s;
-    if (int s = phz_reserve(ctx, h->flags, 64)) return s;
+    if (int s = reserve_all(ctx, {{h->hkeys, slots * 8}, {h->flags, 64}})) return s;
     hipStream_t sm = ctx->stream;
     PHZ_HIP(ctx, hipMemsetAsync(h->hkeys.p, 0xff, slots * 8, sm));
     PHZ_HIP(ctx, hipMemsetAsync(h->flags.p, 0, 64, sm));
@@ -2243,41 +2249,30 @@ extern "C" int phz_rowsdev_pair_keys(phz_ctx *ctx, phz_rowsdev *h, uint64_t *key
     const bool pre_k = pre && h->have_shards && getenv("PHZ_ROWS_NO_PREKEYS") == nullptr;
     unsigned long long h_gap = 0; uint32_t h_nkeys = 0;
     if (pre) {
-        const size_t NV = (size_t)nv, NE = (size_t)(ne ? ne : 1);
-        if (int s = phz_reserve(ctx, h->cnt64, 64)) return s;
-        if (int s = phz_reserve(ctx, h->f_d, NV * 4)) return s;
-        if (int s = phz_reserve(ctx, h->keypos, (NV + 1) * 4)) return s;
-        if (int s = phz_reserve(ctx, h->f_a, std::max(NV, NE) * 4)) return s;          // (the sizes phz_rowsdev_run asks for: its own reservations must not move these buffers)
+        if (int s = reserve_shared(ctx, h)) return s;
         PHZ_HIP(ctx, hipMemsetAsync(h->cnt64.p, 0, 64, sm));
         hipLaunchKernelGGL(k_flag_keys, dim3(std::min(nblk(nv), 512u)), dim3(256), 0, sm, nv, (const long long *)T.var_first, P<uint32_t>(h->f_d), (const unsigned long long *)T.var_rank,
                            P<unsigned long long>(h->cnt64) + 2);
         if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_d), P<uint32_t>(h->keypos), nv, h->scan_tmp)) return s;
     }
-    uint32_t fl = 0;
-    {
-        PhzMail mail(ctx);
-        const int m_gap = pre ? mail.add(P<unsigned long long>(h->cnt64) + 2, 8) : -1, m_fl = mail.add(h->flags.p, 4);
-        const int m_nk = pre_k ? mail.add(P<uint32_t>(h->keypos) + nv, 4) : -1;
-        if (int s = mail.send()) return s;
-        PHZ_HIP(ctx, hipMemcpyAsync(keys_host, h->hkeys.p, slots * 8, hipMemcpyDeviceToHost, sm));          // (copied before the verdict on the table is known -- one wait instead of two;
-        PHZ_HIP(ctx, hipStreamSynchronize(sm));                                                             //  the caller hands over page-locked memory)
-        if (pre) h_gap = *mail.at<unsigned long long>(m_gap);
-        if (pre_k) h_nkeys = *mail.at<uint32_t>(m_nk);
-        fl = *mail.at<uint32_t>(m_fl);
-    }
-    if (fl & 1u) return phz_fail(ctx, PHZ_E_CAPACITY, "the distinct (supporting, total) read-count pairs do not fit the pair-key table: grow it (phz_rowsdev_set_pair_slots) and call again");
+    PhzMail mail(ctx);
+    const int m_gap = pre ? mail.add(P<unsigned long long>(h->cnt64) + 2, 8) : -1, m_fl = mail.add(h->flags.p, 4);
+    const int m_nk = pre_k ? mail.add(P<uint32_t>(h->keypos) + nv, 4) : -1;
+    if (int s = mail.send()) return s;
+    PHZ_HIP(ctx, hipMemcpyAsync(keys_host, h->hkeys.p, slots * 8, hipMemcpyDeviceToHost, sm));          // (copied before the verdict on the table is known -- one wait instead of two;
+    PHZ_HIP(ctx, hipStreamSynchronize(sm));                                                             //  the caller hands over page-locked memory)
+    if (pre) h_gap = *mail.at<unsigned long long>(m_gap);
+    if (pre_k) h_nkeys = *mail.at<uint32_t>(m_nk);
+    if (*mail.at<uint32_t>(m_fl) & 1u) return phz_fail(ctx, PHZ_E_CAPACITY, "the distinct (supporting, total) read-count pairs do not fit the pair-key table: grow it (phz_rowsdev_set_pair_slots) and call again");
     if (pre) {
         // ... and the ordering sorts that need no p-value are on the stream before this call returns: they run while the caller evaluates scipy on the keys
         if (int s = order_variants_and_pairs(ctx, h, h_gap)) return s;
         h->pre_done = true; h->pre_max_gap = h_gap; h->pre_gen = ctx->tally_gen;
         if (pre_k) {
             // ... and the first-appearance keys: the per-chromosome counter / segment-start tables are cleared HERE (phz_rowsdev_run leaves them alone when it finds the keys done)
-            const int nchrom = h->nchrom, nb = T.nb, nsh = (int)h->sh_bam.size();
-            const size_t n_cc = n_chrom_counters(nchrom, nb);
-            if (int s = phz_reserve(ctx, h->chrom_cnt, n_cc * 4 + 8 + (size_t)nchrom * 8)) return s;
-            if (int s = phz_reserve(ctx, h->seg_start, (n_cc + 1) * 4)) return s;
+            const int nsh = (int)h->sh_bam.size();
             PHZ_HIP(ctx, hipMemsetAsync(h->chrom_cnt.p, 0, h->chrom_cnt.cap, sm));
-            PHZ_HIP(ctx, hipMemsetAsync(h->seg_start.p, 0xff, (n_cc + 1) * 4, sm));
+            PHZ_HIP(ctx, hipMemsetAsync(h->seg_start.p, 0xff, ChromLayout{h->nchrom, T.nb}.start_bytes(), sm));
             const size_t one = ((size_t)nsh * 8 + 255) & ~(size_t)255;
             if (int s = phz_reserve_host(ctx, h->sh_host, 3 * one + 256)) return s;          // (page-locked, the handle's own: the copy below may still be queued when the caller comes back)
             if (int s = phz_reserve(ctx, h->sh_dev, 3 * one + 256)) return s;
@@ -2285,9 +2280,8 @@ extern "C" int phz_rowsdev_pair_keys(phz_ctx *ctx, phz_rowsdev *h, uint64_t *key
             for (int i = 0; i < nsh; i++) { ((long long *)hp)[i] = h->sh_lo[(size_t)i]; ((long long *)(hp + one))[i] = h->sh_hi[(size_t)i]; ((int32_t *)(hp + 2 * one))[i] = h->sh_bam[(size_t)i]; }
             PHZ_HIP(ctx, hipMemcpyAsync(h->sh_dev.p, hp, 3 * one, hipMemcpyHostToDevice, sm));
             const char *dp = (const char *)h->sh_dev.p;
-            uint32_t *cc = P<uint32_t>(h->chrom_cnt), *ss = P<uint32_t>(h->seg_start);
-            if (int s = key_stage(ctx, h, (int64_t)h_nkeys, (const long long *)dp, (const long long *)(dp + one), (const int32_t *)(dp + 2 * one), nsh,
-                                  ss + 3 * (size_t)nchrom, cc + 3 * (size_t)nchrom)) return s;
+            const ShardTab ST{(const long long *)dp, (const long long *)(dp + one), (const int32_t *)(dp + 2 * one), nsh};
+            if (int s = key_stage(ctx, h, (int64_t)h_nkeys, ST)) return s;
             h->pre_keys = true; h->pre_nkeys = (int64_t)h_nkeys;
         }
     }
@@ -2314,477 +2308,463 @@ extern "C" int phz_tally_pairs(phz_ctx *ctx, const phz_lines *shards, int n_shar
     return PHZ_OK;
 }
 
-// Stage 2: everything else, up to the finished text in HBM.
-extern "C" int phz_rowsdev_run(phz_ctx *ctx, phz_rowsdev *h, const phz_rowsdev_opts *o, const double *slot_pv, const uint32_t *slot_txt_off,
-                               const char *slot_txt, phz_rowsdev_result *res) {
-    PhzEnter phz_guard_(ctx);
-    if (!ctx || !h || !o || !slot_pv || !slot_txt_off || !slot_txt || !res) return PHZ_E_ARG;
-    auto &T = ctx->tally;
-    if (!h->keys_ready) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run without phz_rowsdev_pair_keys");
-    h->keys_ready = false;
-    if (h->pre_done && h->pre_gen != ctx->tally_gen) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run: the resident tally changed since phz_rowsdev_pair_keys (call it again)");
-    // the first-appearance keys of the first stage count only for exactly the shards this call names
-    bool pre_keys = h->pre_keys && h->pre_done && (int)h->sh_bam.size() == o->n_shards;
-    for (int i = 0; pre_keys && i < o->n_shards; i++)
-        pre_keys = h->sh_lo[(size_t)i] == (long long)o->shard_line_lo[i] && h->sh_hi[(size_t)i] == (long long)o->shard_line_hi[i] && h->sh_bam[(size_t)i] == o->shard_bam[i];
-    h->pre_keys = false;
-    if (T.nv != h->nv || T.nb != o->n_bams) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev: the resident tally does not match (variants / BAMs)");
-    if (o->gw_phase_method != 0 && o->gw_phase_method != 1) return phz_fail(ctx, PHZ_E_ARG, "device row stage: gw_phase_method must be 0 or 1");
-    const bool read_ids = o->output_read_ids != 0;
-    if (read_ids && (!o->qname_off || !o->qname || !o->qname_base)) return phz_fail(ctx, PHZ_E_ARG, "device row stage: --output_read_ids 1 needs the QNAME pool (qname_off / qname / qname_base)");
-    if (!T.rl_list && T.n_rl) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev: the resident tally carries no list index per read-list entry");
-    PHZ_HIP(ctx, hipSetDevice(ctx->device));
-    memset(res, 0, sizeof(*res));
-    hipStream_t sm = ctx->stream;
-    const int64_t nv = T.nv, ne = T.n_edges, n_rl = T.n_rl, n_lines = T.n_lines;
-    const int nb = T.nb, nchrom = h->nchrom;
-    const size_t NV = (size_t)(nv ? nv : 1), NE = (size_t)(ne ? ne : 1), NRL = NV * 2 * (size_t)nb, NR = (size_t)(n_rl ? n_rl : 1);
-    const int32_t *cis = T.stats, *trans = T.stats + ne, *sup = T.stats + 2 * ne, *tot = T.stats + 3 * ne, *cfgv = T.stats + 4 * ne;
-    Sections sec(ctx);
-    sec.begin();
-    // ---- per-pass uploads
-    const size_t ps_slots = (size_t)h->ps_slots;
-    // ONE copy for all of them: gathered in a page-locked block (a hipMemcpyAsync from the caller's pageable arrays is staged synchronously, 10-20 us each
-    // -- nine of them were a third of this stage's first section, which is bound by what the host can enqueue), 256-byte aligned pieces of one device block
-    const void *up_src[9] = {slot_pv, slot_txt_off, slot_txt, o->bam_name_off, o->bam_names, o->bam_excluded, o->shard_line_lo, o->shard_line_hi, o->shard_bam};
-    const size_t up_n[9] = {ps_slots * 8, (ps_slots + 1) * 4, (size_t)slot_txt_off[ps_slots], (size_t)(nb + 1) * 4, (size_t)o->bam_name_off[nb], o->bam_excluded ? (size_t)nb : 0,
-                            (size_t)o->n_shards * 8, (size_t)o->n_shards * 8, (size_t)o->n_shards * 4};
-    size_t up_off[10]; up_off[0] = 0;
-    for (int i = 0; i < 9; i++) up_off[i + 1] = up_off[i] + ((up_n[i] + 255) & ~(size_t)255);
-    if (int s = phz_reserve_host(ctx, h->up_host, up_off[9] + 256)) return s;
-    if (int s = phz_reserve(ctx, h->up_dev, up_off[9] + 256)) return s;
-    for (int i = 0; i < 9; i++) if (up_n[i]) memcpy((char *)h->up_host.p + up_off[i], up_src[i], up_n[i]);
-    PHZ_HIP(ctx, hipMemcpyAsync(h->up_dev.p, h->up_host.p, up_off[9], hipMemcpyHostToDevice, sm));
-    const char *upd = (const char *)h->up_dev.p;
-    const double *d_slot_pv = (const double *)(upd + up_off[0]); const uint32_t *d_pv_off = (const uint32_t *)(upd + up_off[1]); const char *d_pv_txt = upd + up_off[2];
-    const uint32_t *d_bam_off = (const uint32_t *)(upd + up_off[3]); const char *d_bam_txt = upd + up_off[4]; const uint8_t *d_bam_excl = (const uint8_t *)(upd + up_off[5]);
-    const long long *d_sh_lo = (const long long *)(upd + up_off[6]), *d_sh_hi = (const long long *)(upd + up_off[7]); const int32_t *d_sh_bam = (const int32_t *)(upd + up_off[8]);
-    if (read_ids) {          // (a debugging option: plain uploads)
-        const size_t nq = (size_t)o->qname_base[nchrom];
-        if (int s = up(ctx, h->qn_off, o->qname_off, (nq + 1) * 4)) return s;
-        if (int s = up(ctx, h->qn_txt, o->qname, (size_t)o->qname_off[nq])) return s;
-        if (int s = up(ctx, h->qn_base, o->qname_base, (size_t)(nchrom + 1) * 8)) return s;
-        PHZ_HIP(ctx, hipStreamSynchronize(sm));          // the caller's arrays are pageable
+// ---------------------------------------------------------------------------------------------- stage 2: everything else, up to the finished text in HBM
+namespace {
+// per-chromosome segments of the files: rows of a segment = counter of chrom_cnt x (1 or the number of BAMs); k_seg_offsets turns them into byte offsets
+const struct { uint32_t *ChromTab::*count; bool times_bams; } SEG_ROWS[PHZ_TXT_COUNT] = {
+    {&ChromTab::conn, false}, {&ChromTab::blocks, false}, {&ChromTab::blocks, true}, {&ChromTab::blocks, false},          // conn, hap, ase, cfg
+    {&ChromTab::keys, false}, {&ChromTab::keys, true}, {&ChromTab::keys, false}};                                            // allelic, single_ase, single_hap
+const int WRITE_ORDER[PHZ_TXT_COUNT] = {PHZ_TXT_CFG, PHZ_TXT_ASE, PHZ_TXT_ALLELIC, PHZ_TXT_CONN, PHZ_TXT_HAP, PHZ_TXT_SINGLE_ASE, PHZ_TXT_SINGLE_HAP};          // largest file first (copy-as-written)
+enum Wave { NO_WAVE, WAVE_PER_BLOCK, WAVE_PER_BLOCK_BAM };          // which rows of a file a wave formats: none / one per big block / one per (big block, BAM)
+// What one phz_rowsdev_run call knows.  Its stage functions are the sync-free sections of the pass in stream order, each named after the host wait it ends in; what a
+// stage reads back at its wait stays here for the stages after it.
+struct Pass {
+    phz_ctx *ctx; phz_rowsdev *h; const phz_rowsdev_opts *o; phz_rowsdev_result *res; decltype(phz_ctx::tally) &T; hipStream_t sm; Sections sec;
+    const int64_t nv, ne, n_rl; const int nb, nchrom; const size_t NV, NE, NRL, NR;          // sizes of the resident tally
+    const int32_t *cis, *trans, *sup, *tot, *cfgv; bool read_ids = false, pre_keys = false, need_all = false;
+    // typed views of the upload block (up_dev)
+    const double *d_slot_pv = nullptr; const uint32_t *d_pv_off = nullptr, *d_bam_off = nullptr; const char *d_pv_txt = nullptr, *d_bam_txt = nullptr; const uint8_t *d_bam_excl = nullptr; ShardTab shards;
+    // counters: cnt32 [0..15] counters of the stages, [16] ticket of k_phase_general, [20] pool overflow of the read-set stage, [32 + 16 m ..] counters and tickets of its mode m
+    const ChromLayout lay; ChromTab cc, ss; unsigned long long *cc_cfg = nullptr, *cnt64 = nullptr; uint32_t *cnt32 = nullptr;
+    int64_t nmem = 0, ncomp = 0, nkeep = 0, nkeys = 0, n_linked = 0; unsigned long long max_gap = 0;          // read at "sizes: members/comps/kept/keys"
+    int64_t nblocks = 0;          // read at "phase + blocks: count"
+    uint32_t h_nbig = 0, h_nbs = 0; unsigned long long h_cfg_total = 0; std::vector<uint32_t> h_cc;          // read at "stats + read sets + text sizes"
+    RD D; int64_t rows[PHZ_TXT_COUNT];          // what the row kernels read; rows per file
+    struct CopyGuard {          // whatever way this call ends, no copy into the caller's region is still in flight when it returns
+        phz_ctx *c; bool armed = false;
+        ~CopyGuard() { if (armed && c->copy_stream) (void)hipStreamSynchronize(c->copy_stream); }
+    } copy_guard;
+    Pass(phz_ctx *ctx_, phz_rowsdev *h_, const phz_rowsdev_opts *o_, phz_rowsdev_result *res_)
+        : ctx(ctx_), h(h_), o(o_), res(res_), T(ctx_->tally), sm(ctx_->stream), sec(ctx_), nv(T.nv), ne(T.n_edges), n_rl(T.n_rl), nb(T.nb), nchrom(h_->nchrom),
+          NV((size_t)(nv ? nv : 1)), NE((size_t)(ne ? ne : 1)), NRL(NV * 2 * (size_t)nb), NR((size_t)(n_rl ? n_rl : 1)),
+          cis(T.stats), trans(T.stats + ne), sup(T.stats + 2 * ne), tot(T.stats + 3 * ne), cfgv(T.stats + 4 * ne), lay{h_->nchrom, T.nb}, copy_guard{ctx_} {}
+    int seg_count(int f) const { return SEG_ROWS[f].count == &ChromTab::keys ? nb * nchrom : nchrom; }
+    int check_and_upload(const double *slot_pv, const uint32_t *slot_txt_off, const char *slot_txt) {
+        if (!h->keys_ready) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run without phz_rowsdev_pair_keys");
+        h->keys_ready = false;
+        if (h->pre_done && h->pre_gen != ctx->tally_gen) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run: the resident tally changed since phz_rowsdev_pair_keys (call it again)");
+        // the first-appearance keys of the first stage count only for exactly the shards this call names
+        pre_keys = h->pre_keys && h->pre_done && (int)h->sh_bam.size() == o->n_shards;
+        for (int i = 0; pre_keys && i < o->n_shards; i++)
+            pre_keys = h->sh_lo[(size_t)i] == (long long)o->shard_line_lo[i] && h->sh_hi[(size_t)i] == (long long)o->shard_line_hi[i] && h->sh_bam[(size_t)i] == o->shard_bam[i];
+        h->pre_keys = false;
+        if (T.nv != h->nv || T.nb != o->n_bams) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev: the resident tally does not match (variants / BAMs)");
+        if (o->gw_phase_method != 0 && o->gw_phase_method != 1) return phz_fail(ctx, PHZ_E_ARG, "device row stage: gw_phase_method must be 0 or 1");
+        read_ids = o->output_read_ids != 0;
+        if (read_ids && (!o->qname_off || !o->qname || !o->qname_base)) return phz_fail(ctx, PHZ_E_ARG, "device row stage: --output_read_ids 1 needs the QNAME pool (qname_off / qname / qname_base)");
+        if (!T.rl_list && T.n_rl) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev: the resident tally carries no list index per read-list entry");
+        PHZ_HIP(ctx, hipSetDevice(ctx->device));
+        memset(res, 0, sizeof(*res));
+        need_all = nb > 1 || h->has_black;
+        sec.begin();
+        const size_t ps_slots = (size_t)h->ps_slots;
+        // ONE copy for all of them: gathered in a page-locked block (a hipMemcpyAsync from the caller's pageable arrays is staged synchronously, 10-20 us each
+        // -- nine of them were a third of this stage's first section, which is bound by what the host can enqueue), 256-byte aligned pieces of one device block
+        const void *up_src[9] = {slot_pv, slot_txt_off, slot_txt, o->bam_name_off, o->bam_names, o->bam_excluded, o->shard_line_lo, o->shard_line_hi, o->shard_bam};
+        const size_t up_n[9] = {ps_slots * 8, (ps_slots + 1) * 4, (size_t)slot_txt_off[ps_slots], (size_t)(nb + 1) * 4, (size_t)o->bam_name_off[nb], o->bam_excluded ? (size_t)nb : 0,
+                                (size_t)o->n_shards * 8, (size_t)o->n_shards * 8, (size_t)o->n_shards * 4};
+        size_t up_off[10]; up_off[0] = 0;
+        for (int i = 0; i < 9; i++) up_off[i + 1] = up_off[i] + ((up_n[i] + 255) & ~(size_t)255);
+        if (int s = phz_reserve_host(ctx, h->up_host, up_off[9] + 256)) return s;
+        if (int s = phz_reserve(ctx, h->up_dev, up_off[9] + 256)) return s;
+        for (int i = 0; i < 9; i++) if (up_n[i]) memcpy((char *)h->up_host.p + up_off[i], up_src[i], up_n[i]);
+        PHZ_HIP(ctx, hipMemcpyAsync(h->up_dev.p, h->up_host.p, up_off[9], hipMemcpyHostToDevice, sm));
+        const char *upd = (const char *)h->up_dev.p;
+        d_slot_pv = (const double *)(upd + up_off[0]); d_pv_off = (const uint32_t *)(upd + up_off[1]); d_pv_txt = upd + up_off[2];
+        d_bam_off = (const uint32_t *)(upd + up_off[3]); d_bam_txt = upd + up_off[4]; d_bam_excl = (const uint8_t *)(upd + up_off[5]);
+        shards.lo = (const long long *)(upd + up_off[6]); shards.hi = (const long long *)(upd + up_off[7]); shards.bam = (const int32_t *)(upd + up_off[8]); shards.n = o->n_shards;
+        if (read_ids) {          // (a debugging option: plain uploads)
+            const size_t nq = (size_t)o->qname_base[nchrom];
+            if (int s = up(ctx, h->qn_off, o->qname_off, (nq + 1) * 4)) return s;
+            if (int s = up(ctx, h->qn_txt, o->qname, (size_t)o->qname_off[nq])) return s;
+            if (int s = up(ctx, h->qn_base, o->qname_base, (size_t)(nchrom + 1) * 8)) return s;
+            PHZ_HIP(ctx, hipStreamSynchronize(sm));          // the caller's arrays are pageable
+        }
+        return PHZ_OK;
     }
-    // ---- pruning (:686-700) + components
-#define RSV(buf, bytes) do { if (int s_ = phz_reserve(ctx, h->buf, (bytes))) return s_; } while (0)
-    RSV(keep, NE); RSV(e_slot, NE * 4); RSV(deg, NV * 4); RSV(parent, NV * 4); RSV(label, NV * 4);
-    RSV(cnt64, 64); RSV(cnt32, 512);          // cnt32: [0..15] counters of the stages, [16] ticket of k_phase_general, [20] pool overflow of the read-set stage, [32 + 16 m ..] counters and tickets of its mode m
-    const size_t n_cc = (size_t)nchrom * 3 + (size_t)nb * nchrom;          // uint32 counters per chromosome, then uint64 cfg rows per chromosome
-    RSV(chrom_cnt, n_cc * 4 + 8 + (size_t)nchrom * 8);
-    uint32_t *cc_conn = P<uint32_t>(h->chrom_cnt), *cc_blocks = cc_conn + nchrom, *cc_blkvars = cc_blocks + nchrom, *cc_keys = cc_blkvars + nchrom;
-    unsigned long long *cc_cfg = (unsigned long long *)((char *)h->chrom_cnt.p + ((n_cc * 4 + 7) & ~(size_t)7));
-    if (!pre_keys) PHZ_HIP(ctx, hipMemsetAsync(h->chrom_cnt.p, 0, h->chrom_cnt.cap, sm));          // (pre_keys: cleared by the first stage, the key counters are in)
-    RSV(seg_start, (n_cc + 1) * 4);            // first row of every segment, same layout as the counters
-    uint32_t *ss_conn = P<uint32_t>(h->seg_start), *ss_blocks = ss_conn + nchrom, *ss_keys = ss_blocks + 2 * nchrom;
-    if (!pre_keys) PHZ_HIP(ctx, hipMemsetAsync(h->seg_start.p, 0xff, (n_cc + 1) * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->deg.p, 0, NV * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->cnt64.p, 0, 64, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->cnt32.p, 0, 512, sm));
-    unsigned long long *cnt64 = P<unsigned long long>(h->cnt64);
-    uint32_t *cnt32 = P<uint32_t>(h->cnt32);
-    if (ne) hipLaunchKernelGGL(k_keep, dim3(std::min(nblk(ne), 2048u)), dim3(256), 0, sm, ne, (const uint8_t *)T.linked, sup, tot, (const unsigned long long *)h->hkeys.p, (uint32_t)(ps_slots - 1),
-                               d_slot_pv, o->cc_threshold, P<uint8_t>(h->keep), P<uint32_t>(h->e_slot), P<uint32_t>(h->deg), (const int32_t *)T.ea,
-                               (const int32_t *)T.eb, cnt64);
-    if (nv) hipLaunchKernelGGL(k_uf_init, dim3(nblk(nv)), dim3(256), 0, sm, P<int32_t>(h->parent), nv);
-    if (ne) hipLaunchKernelGGL(k_uf_hook, dim3(nblk(ne)), dim3(256), 0, sm, P<int32_t>(h->parent), (const int32_t *)T.ea, (const int32_t *)T.eb, (const uint8_t *)h->keep.p, ne);
-    if (nv) hipLaunchKernelGGL(k_uf_flatten, dim3(nblk(nv)), dim3(256), 0, sm, P<int32_t>(h->parent), P<int32_t>(h->label), nv);
-    // ---- sizes of the compacted lists: members, components, kept pairs, first-appearance keys
-    RSV(f_a, std::max(NV, NE) * 4); RSV(f_b, NV * 4); RSV(f_c, NE * 4); RSV(f_d, NV * 4);
-    RSV(mem_pos, (NV + 1) * 4); RSV(cid, (NV + 1) * 4); RSV(kpos, (NE + 1) * 4); RSV(keypos, (NV + 1) * 4);
-    if (nv) hipLaunchKernelGGL(k_flag_members, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)h->deg.p, (const int32_t *)h->label.p, P<uint32_t>(h->f_a), P<uint32_t>(h->f_b));
-    if (ne) hipLaunchKernelGGL(k_flag_u8, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint8_t *)h->keep.p, P<uint32_t>(h->f_c));
-    if (nv && !h->pre_done) hipLaunchKernelGGL(k_flag_keys, dim3(std::min(nblk(nv), 512u)), dim3(256), 0, sm, nv, (const long long *)T.var_first, P<uint32_t>(h->f_d), (const unsigned long long *)T.var_rank, cnt64 + 2);
-    if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_a), P<uint32_t>(h->mem_pos), nv, h->scan_tmp)) return s;
-    if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_b), P<uint32_t>(h->cid), nv, h->scan_tmp)) return s;
-    if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_c), P<uint32_t>(h->kpos), ne, h->scan_tmp)) return s;
-    if (!h->pre_done) { if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_d), P<uint32_t>(h->keypos), nv, h->scan_tmp)) return s; }
-    PHZ_HIP(ctx, hipGetLastError());
-    uint32_t h_n[4] = {0, 0, 0, 0}; unsigned long long h_c64[8] = {0};
-    {
+    // ---- pruning (:686-700) + components; sizes of the compacted lists: members, components, kept pairs, first-appearance keys
+    int sizes() {
+        if (int s = reserve_shared(ctx, h)) return s;
+        if (int s = reserve_all(ctx, {{h->keep, NE}, {h->e_slot, NE * 4}, {h->deg, NV * 4}, {h->parent, NV * 4}, {h->label, NV * 4}, {h->cnt32, 512},
+                                      {h->f_b, NV * 4}, {h->f_c, NE * 4}, {h->mem_pos, (NV + 1) * 4}, {h->cid, (NV + 1) * 4}, {h->kpos, (NE + 1) * 4}})) return s;
+        cc = lay.tab(h->chrom_cnt.p); ss = lay.tab(h->seg_start.p); cc_cfg = lay.cfg_rows(h->chrom_cnt.p); cnt64 = P<unsigned long long>(h->cnt64); cnt32 = P<uint32_t>(h->cnt32);
+        if (!pre_keys) PHZ_HIP(ctx, hipMemsetAsync(h->chrom_cnt.p, 0, h->chrom_cnt.cap, sm));          // (pre_keys: cleared by the first stage, the key counters are in)
+        if (!pre_keys) PHZ_HIP(ctx, hipMemsetAsync(h->seg_start.p, 0xff, lay.start_bytes(), sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->deg.p, 0, NV * 4, sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->cnt64.p, 0, 64, sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->cnt32.p, 0, 512, sm));
+        if (ne) hipLaunchKernelGGL(k_keep, dim3(std::min(nblk(ne), 2048u)), dim3(256), 0, sm, ne, (const uint8_t *)T.linked, sup, tot, (const unsigned long long *)h->hkeys.p, (uint32_t)(h->ps_slots - 1),
+                                   d_slot_pv, o->cc_threshold, P<uint8_t>(h->keep), P<uint32_t>(h->e_slot), P<uint32_t>(h->deg), (const int32_t *)T.ea,
+                                   (const int32_t *)T.eb, cnt64);
+        if (nv) hipLaunchKernelGGL(k_uf_init, dim3(nblk(nv)), dim3(256), 0, sm, P<int32_t>(h->parent), nv);
+        if (ne) hipLaunchKernelGGL(k_uf_hook, dim3(nblk(ne)), dim3(256), 0, sm, P<int32_t>(h->parent), (const int32_t *)T.ea, (const int32_t *)T.eb, (const uint8_t *)h->keep.p, ne);
+        if (nv) hipLaunchKernelGGL(k_uf_flatten, dim3(nblk(nv)), dim3(256), 0, sm, P<int32_t>(h->parent), P<int32_t>(h->label), nv);
+        if (nv) hipLaunchKernelGGL(k_flag_members, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)h->deg.p, (const int32_t *)h->label.p, P<uint32_t>(h->f_a), P<uint32_t>(h->f_b));
+        if (ne) hipLaunchKernelGGL(k_flag_u8, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint8_t *)h->keep.p, P<uint32_t>(h->f_c));
+        if (nv && !h->pre_done) hipLaunchKernelGGL(k_flag_keys, dim3(std::min(nblk(nv), 512u)), dim3(256), 0, sm, nv, (const long long *)T.var_first, P<uint32_t>(h->f_d), (const unsigned long long *)T.var_rank, cnt64 + 2);
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_a), P<uint32_t>(h->mem_pos), nv, h->scan_tmp)) return s;
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_b), P<uint32_t>(h->cid), nv, h->scan_tmp)) return s;
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_c), P<uint32_t>(h->kpos), ne, h->scan_tmp)) return s;
+        if (!h->pre_done) { if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->f_d), P<uint32_t>(h->keypos), nv, h->scan_tmp)) return s; }
+        PHZ_HIP(ctx, hipGetLastError());
         PhzMail mail(ctx);
         const int m[5] = {mail.add(P<uint32_t>(h->mem_pos) + nv, 4), mail.add(P<uint32_t>(h->cid) + nv, 4), mail.add(P<uint32_t>(h->kpos) + ne, 4),
                           mail.add(P<uint32_t>(h->keypos) + nv, 4), mail.add(cnt64, 24)};
         if (int s = mail.send()) return s;
         if (int s = sec.wait("sizes: members/comps/kept/keys")) return s;
-        for (int i = 0; i < 4; i++) h_n[i] = *mail.at<uint32_t>(m[i]);
-        memcpy(h_c64, mail.at<char>(m[4]), 24);
+        nmem = *mail.at<uint32_t>(m[0]); ncomp = *mail.at<uint32_t>(m[1]); nkeep = *mail.at<uint32_t>(m[2]); nkeys = *mail.at<uint32_t>(m[3]);
+        const unsigned long long *c64 = mail.at<unsigned long long>(m[4]); n_linked = (int64_t)c64[0]; res->dropped = (int64_t)c64[1];
+        max_gap = h->pre_done ? h->pre_max_gap : c64[2];          // (pre_done: measured by the first stage; this run's counters were cleared after it)
+        sec.begin();
+        return PHZ_OK;
     }
-    if (h->pre_done) h_c64[2] = h->pre_max_gap;          // (measured by the first stage; this run's counters were cleared after it)
-    const int64_t nmem = h_n[0], ncomp = h_n[1], nkeep = h_n[2], nkeys = h_n[3], n_linked = (int64_t)h_c64[0];
-    res->dropped = (int64_t)h_c64[1];
-    sec.begin();
     // ---- ordering stage: rank index of every variant, pair order, members by component, component order, kept pairs by component, keys
-    const int bv = bits_for((uint64_t)(nv > 1 ? nv - 1 : 1));
-    int bl = bits_for((uint64_t)(n_lines > 1 ? n_lines - 1 : 1));
-    if (const char *fb = getenv("PHZ_ROWS_FAKE_LINE_BITS")) bl = std::max(bl, std::min(32, atoi(fb)));      // tests: the key layout of a BAM with > 2^31 call lines
-    const size_t NS = std::max(NV, NE);
-    RSV(k64a, NS * 8); RSV(k64b, NS * 8); RSV(k32a, NS * 4); RSV(k32b, NS * 4); RSV(v32a, NS * 4); RSV(v32b, NS * 4);
-    RSV(ridx, NV * 4); RSV(va, NE * 4); RSV(vb, NE * 4); RSV(eorder, NE * 4);
-    RSV(mem_s, (size_t)(nmem + 1) * 4); RSV(cstart, (size_t)(ncomp + 2) * 4); RSV(corder, (size_t)(ncomp + 1) * 4); RSV(ekeep, (size_t)(nkeep + 1) * 4);
-    RSV(estart, (size_t)(ncomp + 2) * 4); RSV(key_g, (size_t)(nkeys + 1) * 4);
-    if (!h->pre_done) { if (int s = order_variants_and_pairs(ctx, h, h_c64[2])) return s; }
-    h->pre_done = false;
-    if (ne) {
-        if (n_linked) hipLaunchKernelGGL(k_conn_starts, dim3(nblk(n_linked)), dim3(256), 0, sm, n_linked, (const uint32_t *)h->eorder.p, (const int32_t *)h->va.p,
-                                         (const uint16_t *)h->d_vchrom.p, ss_conn);
-    }
-    hipLaunchKernelGGL(k_starts_to_counts, dim3(1), dim3(1), 0, sm, ss_conn, nchrom, (uint32_t)n_linked, cc_conn);
-    {
-    }
-    if (nmem) {
-        hipLaunchKernelGGL(k_compact_members, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)h->deg.p, (const uint32_t *)h->mem_pos.p, (const int32_t *)h->label.p,
-                           P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
-        const int rg[1][2] = {{0, bv}};
-        if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, nmem, rg, 1, P<uint32_t>(h->mem_s), P<uint32_t>(h->f_a))) return s;         // f_a: sorted labels
-        hipLaunchKernelGGL(k_group_starts, dim3(nblk(nmem)), dim3(256), 0, sm, nmem, (const uint32_t *)h->f_a.p, (const uint32_t *)h->cid.p, P<uint32_t>(h->cstart));
-        hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, P<uint32_t>(h->cstart) + ncomp, (int64_t)1, (uint32_t)nmem);
-        hipLaunchKernelGGL(k_comp_min, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, (const uint32_t *)h->cstart.p, (const uint32_t *)h->mem_s.p, (const uint32_t *)h->ridx.p,
-                           P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
-        if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, ncomp, rg, 1, P<uint32_t>(h->corder), nullptr)) return s;
-        hipLaunchKernelGGL(k_compact_kept, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint8_t *)h->keep.p, (const uint32_t *)h->kpos.p, (const int32_t *)T.ea,
-                           (const int32_t *)h->label.p, (const uint32_t *)h->cid.p, P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
-        const int rgc[1][2] = {{0, bits_for((uint64_t)(ncomp > 1 ? ncomp - 1 : 1))}};
-        if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, nkeep, rgc, 1, P<uint32_t>(h->ekeep), P<uint32_t>(h->f_a))) return s;        // f_a: component of every kept pair
-        hipLaunchKernelGGL(k_group_starts, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, (const uint32_t *)h->f_a.p, (const uint32_t *)nullptr, P<uint32_t>(h->estart));
-        hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, P<uint32_t>(h->estart) + ncomp, (int64_t)1, (uint32_t)nkeep);
-    }
-    if (!pre_keys) {          // (else: enqueued by the first stage, under the caller's p-value evaluation)
-        if (int s = key_stage(ctx, h, nkeys, d_sh_lo, d_sh_hi, d_sh_bam, o->n_shards, ss_keys, cc_keys)) return s;
-    } else if (nkeys != h->pre_nkeys) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run: the covered variants changed since phz_rowsdev_pair_keys");
     // ---- block phasing: both kernels behind each other, then -- speculating that no component needs the host (a handful per genome at most) -- the block
     //      numbering, all before ONE host wait; exceptions are phased on the host and the numbering is redone
-    if (int s = phase_enqueue(ctx, h->cstart, h->mem_s, h->estart, h->ekeep, T.ea, T.eb, cfgv, ncomp, nmem, nkeep, o->max_block_size, h->alle_of, h->sub_of, h->nsub,
-                              h->complex_list, h->exc_list, h->eloc, cnt32)) return s;
-    // ---- blocks in block order; per-block statistics
-    const size_t NBK = (size_t)(nmem / 2 + 2);
-    RSV(nsub_o, (size_t)(ncomp + 1) * 4); RSV(blk_base, (size_t)(ncomp + 2) * 4);
-    RSV(blk_mstart, NBK * 4); RSV(blk_len, NBK * 4); RSV(blk_of, NV * 4); RSV(v_alle, NV); RSV(blk_sup, NBK * 4); RSV(blk_tot, NBK * 4);
-    RSV(conc, NBK); RSV(cormode, NBK); RSV(statkind, NBK); RSV(statidx, NBK * 4); RSV(maxmaf, NBK * 4); RSV(stat, NBK * 8); RSV(cfg_rows, NBK * 8);
-    RSV(cfg_base, (NBK + 1) * 8); RSV(blk_voff, (NBK + 1) * 4);
-    PHZ_HIP(ctx, hipMemsetAsync(h->blk_of.p, 0xff, NV * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->v_alle.p, 0, NV, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->blk_sup.p, 0, NBK * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(h->blk_tot.p, 0, NBK * 4, sm));
-    int64_t nblocks = 0;
-    unsigned long long h_cfg_total = 0;
-    std::vector<uint32_t> h_cc(n_cc, 0u); std::vector<unsigned long long> h_cfgc((size_t)nchrom, 0ull);
-    if (ncomp) {
-        uint32_t nb32 = 0, h_c32[4] = {0, 0, 0, 0};
+    int phase_and_blocks() {
+        const int bv = key_bits(ctx).var;
+        if (int s = reserve_all(ctx, {{h->mem_s, (size_t)(nmem + 1) * 4}, {h->cstart, (size_t)(ncomp + 2) * 4}, {h->corder, (size_t)(ncomp + 1) * 4}, {h->ekeep, (size_t)(nkeep + 1) * 4},
+                                      {h->estart, (size_t)(ncomp + 2) * 4}, {h->key_g, (size_t)(nkeys + 1) * 4}})) return s;
+        if (!h->pre_done) { if (int s = order_variants_and_pairs(ctx, h, max_gap)) return s; }
+        h->pre_done = false;
+        if (ne && n_linked) hipLaunchKernelGGL(k_conn_starts, dim3(nblk(n_linked)), dim3(256), 0, sm, n_linked, (const uint32_t *)h->eorder.p, (const int32_t *)h->va.p,
+                                               (const uint16_t *)h->d_vchrom.p, ss.conn);
+        hipLaunchKernelGGL(k_starts_to_counts, dim3(1), dim3(1), 0, sm, ss.conn, nchrom, (uint32_t)n_linked, cc.conn);
+        if (nmem) {
+            hipLaunchKernelGGL(k_compact_members, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)h->deg.p, (const uint32_t *)h->mem_pos.p, (const int32_t *)h->label.p,
+                               P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
+            const int rg[1][2] = {{0, bv}};
+            if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, nmem, rg, 1, P<uint32_t>(h->mem_s), P<uint32_t>(h->f_a))) return s;         // f_a: sorted labels
+            hipLaunchKernelGGL(k_group_starts, dim3(nblk(nmem)), dim3(256), 0, sm, nmem, (const uint32_t *)h->f_a.p, (const uint32_t *)h->cid.p, P<uint32_t>(h->cstart));
+            hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, P<uint32_t>(h->cstart) + ncomp, (int64_t)1, (uint32_t)nmem);
+            hipLaunchKernelGGL(k_comp_min, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, (const uint32_t *)h->cstart.p, (const uint32_t *)h->mem_s.p, (const uint32_t *)h->ridx.p,
+                               P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
+            if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, ncomp, rg, 1, P<uint32_t>(h->corder), nullptr)) return s;
+            hipLaunchKernelGGL(k_compact_kept, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint8_t *)h->keep.p, (const uint32_t *)h->kpos.p, (const int32_t *)T.ea,
+                               (const int32_t *)h->label.p, (const uint32_t *)h->cid.p, P<uint32_t>(h->k32a), P<uint32_t>(h->v32a));
+            const int rgc[1][2] = {{0, bits_for((uint64_t)(ncomp > 1 ? ncomp - 1 : 1))}};
+            if (int s = sort_into<uint32_t>(ctx, h, h->k32a, h->k32b, nkeep, rgc, 1, P<uint32_t>(h->ekeep), P<uint32_t>(h->f_a))) return s;        // f_a: component of every kept pair
+            hipLaunchKernelGGL(k_group_starts, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, (const uint32_t *)h->f_a.p, (const uint32_t *)nullptr, P<uint32_t>(h->estart));
+            hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, P<uint32_t>(h->estart) + ncomp, (int64_t)1, (uint32_t)nkeep);
+        }
+        if (!pre_keys) {          // (else: enqueued by the first stage, under the caller's p-value evaluation)
+            if (int s = key_stage(ctx, h, nkeys, shards)) return s;
+        } else if (nkeys != h->pre_nkeys) return phz_fail(ctx, PHZ_E_ARG, "phz_rowsdev_run: the covered variants changed since phz_rowsdev_pair_keys");
+        const PhaseArgs pa{h->cstart, h->mem_s, h->estart, h->ekeep, T.ea, T.eb, cfgv, ne, ncomp, nmem, nkeep, o->max_block_size, h->alle_of, h->sub_of, h->nsub, h->complex_list, h->exc_list, h->eloc, cnt32};
+        if (int s = phase_enqueue(ctx, pa)) return s;
+        // ---- blocks in block order; per-block statistics
+        const size_t NBK = (size_t)(nmem / 2 + 2);
+        if (int s = reserve_all(ctx, {{h->nsub_o, (size_t)(ncomp + 1) * 4}, {h->blk_base, (size_t)(ncomp + 2) * 4},
+                                      {h->blk_mstart, NBK * 4}, {h->blk_len, NBK * 4}, {h->blk_of, NV * 4}, {h->v_alle, NV}, {h->blk_sup, NBK * 4}, {h->blk_tot, NBK * 4},
+                                      {h->conc, NBK}, {h->cormode, NBK}, {h->statkind, NBK}, {h->statidx, NBK * 4}, {h->maxmaf, NBK * 4}, {h->stat, NBK * 8}, {h->cfg_rows, NBK * 8},
+                                      {h->cfg_base, (NBK + 1) * 8}, {h->blk_voff, (NBK + 1) * 4}})) return s;
+        PHZ_HIP(ctx, hipMemsetAsync(h->blk_of.p, 0xff, NV * 4, sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->v_alle.p, 0, NV, sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->blk_sup.p, 0, NBK * 4, sm));
+        PHZ_HIP(ctx, hipMemsetAsync(h->blk_tot.p, 0, NBK * 4, sm));
+        if (!ncomp) return PHZ_OK;
+        uint32_t h_c32[4] = {0, 0, 0, 0};
         for (int round = 0; round < 2; round++) {
             hipLaunchKernelGGL(k_gather_nsub, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, (const uint32_t *)h->corder.p, (const uint32_t *)h->nsub.p, P<uint32_t>(h->nsub_o));
             if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->nsub_o), P<uint32_t>(h->blk_base), ncomp, h->scan_tmp)) return s;
             PHZ_HIP(ctx, hipGetLastError());
-            {
-                PhzMail mail(ctx);
-                const int m_nb = mail.add(P<uint32_t>(h->blk_base) + ncomp, 4), m_c = mail.add(cnt32, 12);
-                if (int s = mail.send()) return s;
-                if (int s = sec.wait(round ? "blocks: count (after exceptions)" : "phase + blocks: count")) return s;
-                nb32 = *mail.at<uint32_t>(m_nb);
-                if (round == 0) memcpy(h_c32, mail.at<char>(m_c), 12);
-            }
+            PhzMail mail(ctx);
+            const int m_nb = mail.add(P<uint32_t>(h->blk_base) + ncomp, 4), m_c = mail.add(cnt32, 12);
+            if (int s = mail.send()) return s;
+            if (int s = sec.wait(round ? "blocks: count (after exceptions)" : "phase + blocks: count")) return s;
+            nblocks = *mail.at<uint32_t>(m_nb);
+            if (round == 0) memcpy(h_c32, mail.at<char>(m_c), 12);
             sec.begin();
             if (round == 1 || !(h_c32[1] || h_c32[2])) break;
-            if (int s = phase_exceptions(ctx, h_c32, h->cstart, h->mem_s, h->estart, h->ekeep, T.ea, T.eb, cfgv, ncomp, nmem, nkeep, ne, o->max_block_size, h->alle_of, h->sub_of,
-                                         h->nsub, h->exc_list)) return s;
+            if (int s = phase_exceptions(ctx, h_c32, pa)) return s;
         }
         res->n_complex = h_c32[0]; res->n_exceptions = h_c32[1];
-        nblocks = nb32;
-        BK bk; bk.corder = P<uint32_t>(h->corder); bk.blk_base = P<uint32_t>(h->blk_base); bk.cstart = P<uint32_t>(h->cstart); bk.mem_s = P<uint32_t>(h->mem_s);
-        bk.sub_of = P<int32_t>(h->sub_of); bk.alle_of = P<uint8_t>(h->alle_of); bk.blk_mstart = P<uint32_t>(h->blk_mstart); bk.blk_len = P<uint32_t>(h->blk_len);
-        bk.blk_of = P<int32_t>(h->blk_of); bk.v_alle = P<uint8_t>(h->v_alle);
-        hipLaunchKernelGGL(k_blocks, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, bk);
-        if (nkeep) hipLaunchKernelGGL(k_blk_edges, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, (const uint32_t *)h->ekeep.p, (const int32_t *)T.ea, (const int32_t *)T.eb, cfgv,
-                                      (const int32_t *)h->blk_of.p, (const uint8_t *)h->v_alle.p, P<uint32_t>(h->blk_sup), P<uint32_t>(h->blk_tot));
+        return PHZ_OK;
     }
-    if (nblocks) {
-        BS bs; bs.mem_s = P<uint32_t>(h->mem_s); bs.blk_mstart = P<uint32_t>(h->blk_mstart); bs.blk_len = P<uint32_t>(h->blk_len); bs.v_alle = P<uint8_t>(h->v_alle);
-        bs.phase_idx = P<int8_t>(h->d_phase); bs.mafv = P<double>(h->d_maf); bs.conc = P<uint8_t>(h->conc); bs.cormode = P<uint8_t>(h->cormode); bs.statkind = P<uint8_t>(h->statkind);
-        bs.statidx = P<uint32_t>(h->statidx); bs.maxmaf = P<int32_t>(h->maxmaf); bs.stat = P<double>(h->stat); bs.cfg_rows = P<unsigned long long>(h->cfg_rows);
-        RSV(big_stat, (o->gw_phase_method == 1 ? (size_t)nblocks + 2 : (size_t)(nmem / (STAT_N + 1) + 2)) * 8);      // method 0: only blocks beyond the table (more than STAT_N members)
-        bs.big_stat = P<double>(h->big_stat); bs.big_stat_n = cnt32 + 13; bs.gw_phase_method = o->gw_phase_method;
-        hipLaunchKernelGGL(k_blk_stats, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, bs);
-        hipLaunchKernelGGL(k_block_starts, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, (const uint32_t *)h->blk_mstart.p, (const uint32_t *)h->mem_s.p,
-                           (const uint16_t *)h->d_vchrom.p, ss_blocks);
-    }
-    if (int s = gscan_excl<unsigned long long, unsigned long long>(ctx, P<unsigned long long>(h->cfg_rows), P<unsigned long long>(h->cfg_base), nblocks, h->scan_tmp)) return s;
-    if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->blk_len), P<uint32_t>(h->blk_voff), nblocks, h->scan_tmp)) return s;
-    hipLaunchKernelGGL(k_starts_to_counts, dim3(1), dim3(1), 0, sm, ss_blocks, nchrom, (uint32_t)nblocks, cc_blocks);
-    hipLaunchKernelGGL(k_block_counts, dim3(1), dim3(1), 0, sm, (const uint32_t *)ss_blocks, (const uint32_t *)cc_blocks, nchrom, (const uint32_t *)h->blk_voff.p,
-                       (const unsigned long long *)h->cfg_base.p, cc_blkvars, cc_cfg);
-    // (phased variants and the blocks whose gwStat text the table does not hold are read with the next wait, below)
-    // ---- read sets of the haplotypes: labels + distinct counts.  No host wait inside: k_seg_small classifies the segments and counts the lists, the wave /
-    //      workgroup kernels take their lists in ticket order and read the counts on the device; the pool-overflow flag is read with the next wait (rare:
-    //      the pool is grown and the stage redone)
-    const bool need_all = nb > 1 || h->has_black;
-    RSV(labels, NR * 4); RSV(seg_ns, (size_t)(nblocks + 1) * 2 * nb * 4); RSV(big_list, std::max((size_t)(nblocks + 1) * 2 * nb, NRL) * 4 + 4); RSV(big_list2, std::max((size_t)(nblocks + 1) * 2 * nb, NRL) * 4 + 4);
-    if (need_all) RSV(blk_cnt, (size_t)(nblocks + 1) * 2 * 4);
-    if (nb > 1 || read_ids) RSV(single_n, NRL * 4);
-    if (read_ids) { RSV(isf0, NR); RSV(isf2, NR); }
-    if (h->pool.cap == 0) RSV(pool, (size_t)12 << 20);
-    RSV(lab_e, (size_t)(nmem + 1) * 2 * nb * 4);
-    RSV(huge_list, ((size_t)(nmem / (STAT_N + 1) + 2) * 2 * (size_t)nb + 16) * 4);
-    RSV(its, (NR + 1) * 4); RSV(piece_dst, NRL * 8);
-    RSV(big_blk, (size_t)(nblocks + 1) * 4);
-    uint32_t h_nbig = 0, h_phased = 0, h_nbs = 0;
-    for (int attempt = 0;; attempt++) {
-        PHZ_HIP(ctx, hipMemsetAsync(h->labels.p, 0, NR * 4, sm));
-        if (read_ids) { PHZ_HIP(ctx, hipMemsetAsync(h->isf0.p, 0, NR, sm)); PHZ_HIP(ctx, hipMemsetAsync(h->isf2.p, 0, NR, sm)); }
-        if (nmem) hipLaunchKernelGGL(k_lab_e, dim3(nblk(nmem * 2 * nb)), dim3(256), 0, sm, nmem, nb, (const uint32_t *)h->mem_s.p, (const uint8_t *)h->v_alle.p, P<uint32_t>(h->lab_e));
-        SG sg; sg.nb = nb; sg.lab_e = P<uint32_t>(h->lab_e); sg.nmem = nmem; sg.mem_s = P<uint32_t>(h->mem_s); sg.blk_mstart = P<uint32_t>(h->blk_mstart); sg.blk_len = P<uint32_t>(h->blk_len); sg.v_alle = P<uint8_t>(h->v_alle);
-        sg.black = h->has_black ? P<uint8_t>(h->d_black) : nullptr; sg.rl_start = T.rl_start; sg.rl_qid = T.rl_qid; sg.labels = P<uint32_t>(h->labels);
-        sg.big_list = P<uint32_t>(h->big_list); sg.big_list2 = P<uint32_t>(h->big_list2); sg.overflow = cnt32 + 20;
-        sg.huge_list = P<uint32_t>(h->huge_list);
-        sg.pool = P<uint32_t>(h->pool); sg.pool_cap = (uint32_t)std::min<size_t>(h->pool.cap / 4, 0xFFFFFFF0u);
-        PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 20, 0, 4, sm));
-        PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 32, 0, 3 * 64, sm));          // every mode has its own counters: [0..3] list lengths / pool cursor, [4] huge segments, [5..7] tickets -- nothing is
-        for (int mode = 0; mode < 3; mode++) {                             // overwritten, so all of it is read back at the ONE wait below
-            if (mode == 1 && !need_all) continue;
-            if (mode == 2 && nb <= 1 && !read_ids) continue;
-            sg.isf = !read_ids ? nullptr : (mode == 0 ? P<uint8_t>(h->isf0) : (mode == 2 ? P<uint8_t>(h->isf2) : nullptr));
-            sg.nseg = mode == 0 ? nblocks * 2 * nb : (mode == 1 ? nblocks * 2 : (int64_t)NRL);
-            sg.ns = mode == 0 ? P<uint32_t>(h->seg_ns) : (mode == 1 ? P<uint32_t>(h->blk_cnt) : P<uint32_t>(h->single_n));
-            if (sg.nseg == 0) continue;
-            uint32_t *mc = cnt32 + 32 + 16 * mode;
-            sg.counters = mc; sg.huge_count = mc + 4; sg.tickets = mc + 5;
-            const unsigned g = (unsigned)((sg.nseg + 63) / 64);
-            // fixed numbers of workgroups for the list kernels: what a chip holds at once (10 KB / 52 KB of LDS each); a short list leaves most of them with nothing but one ticket
-            const unsigned g_mid = (unsigned)std::min<int64_t>(sg.nseg, 4096), g_large = (unsigned)std::min<int64_t>(sg.nseg, 768), g_huge = (unsigned)std::min<int64_t>(sg.nseg, 64);
-            if (mode == 0) {
-                hipLaunchKernelGGL(k_seg_small<0>, dim3(g), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<0, 512, 64>), dim3(g_mid), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<0, 4096, PHZ_SEG_THREADS>), dim3(g_large), dim3(PHZ_SEG_THREADS), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<0, 4096, PHZ_SEG_THREADS, true>), dim3(g_huge), dim3(PHZ_SEG_THREADS), 0, sm, sg);
-            } else if (mode == 1) {
-                hipLaunchKernelGGL(k_seg_small<1>, dim3(g), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<1, 512, 64>), dim3(g_mid), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<1, 4096, PHZ_SEG_THREADS>), dim3(g_large), dim3(PHZ_SEG_THREADS), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<1, 4096, PHZ_SEG_THREADS, true>), dim3(g_huge), dim3(PHZ_SEG_THREADS), 0, sm, sg);
-            } else {           // (mode 2 has one piece per segment: never huge)
-                hipLaunchKernelGGL(k_seg_small<2>, dim3(g), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<2, 512, 64>), dim3(g_mid), dim3(64), 0, sm, sg);
-                hipLaunchKernelGGL((k_seg_big<2, 4096, PHZ_SEG_THREADS>), dim3(g_large), dim3(PHZ_SEG_THREADS), 0, sm, sg);
+    // ---- the blocks and their statistics, the read sets (redone with a larger pool when it overflowed), the sizes the text stages need
+    int stats_read_sets_text_sizes() {
+        if (ncomp) {
+            BK bk; bk.corder = P<uint32_t>(h->corder); bk.blk_base = P<uint32_t>(h->blk_base); bk.cstart = P<uint32_t>(h->cstart); bk.mem_s = P<uint32_t>(h->mem_s);
+            bk.sub_of = P<int32_t>(h->sub_of); bk.alle_of = P<uint8_t>(h->alle_of); bk.blk_mstart = P<uint32_t>(h->blk_mstart); bk.blk_len = P<uint32_t>(h->blk_len);
+            bk.blk_of = P<int32_t>(h->blk_of); bk.v_alle = P<uint8_t>(h->v_alle);
+            hipLaunchKernelGGL(k_blocks, dim3(nblk(ncomp)), dim3(256), 0, sm, ncomp, bk);
+            if (nkeep) hipLaunchKernelGGL(k_blk_edges, dim3(nblk(nkeep)), dim3(256), 0, sm, nkeep, (const uint32_t *)h->ekeep.p, (const int32_t *)T.ea, (const int32_t *)T.eb, cfgv,
+                                          (const int32_t *)h->blk_of.p, (const uint8_t *)h->v_alle.p, P<uint32_t>(h->blk_sup), P<uint32_t>(h->blk_tot));
+        }
+        if (nblocks) {
+            BS bs; bs.mem_s = P<uint32_t>(h->mem_s); bs.blk_mstart = P<uint32_t>(h->blk_mstart); bs.blk_len = P<uint32_t>(h->blk_len); bs.v_alle = P<uint8_t>(h->v_alle);
+            bs.phase_idx = P<int8_t>(h->d_phase); bs.mafv = P<double>(h->d_maf); bs.conc = P<uint8_t>(h->conc); bs.cormode = P<uint8_t>(h->cormode); bs.statkind = P<uint8_t>(h->statkind);
+            bs.statidx = P<uint32_t>(h->statidx); bs.maxmaf = P<int32_t>(h->maxmaf); bs.stat = P<double>(h->stat); bs.cfg_rows = P<unsigned long long>(h->cfg_rows);
+            if (int s = phz_reserve(ctx, h->big_stat, (o->gw_phase_method == 1 ? (size_t)nblocks + 2 : (size_t)(nmem / (STAT_N + 1) + 2)) * 8)) return s;      // method 0: only blocks beyond the table (more than STAT_N members)
+            bs.big_stat = P<double>(h->big_stat); bs.big_stat_n = cnt32 + 13; bs.gw_phase_method = o->gw_phase_method;
+            hipLaunchKernelGGL(k_blk_stats, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, bs);
+            hipLaunchKernelGGL(k_block_starts, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, (const uint32_t *)h->blk_mstart.p, (const uint32_t *)h->mem_s.p,
+                               (const uint16_t *)h->d_vchrom.p, ss.blocks);
+        }
+        if (int s = gscan_excl<unsigned long long, unsigned long long>(ctx, P<unsigned long long>(h->cfg_rows), P<unsigned long long>(h->cfg_base), nblocks, h->scan_tmp)) return s;
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, P<uint32_t>(h->blk_len), P<uint32_t>(h->blk_voff), nblocks, h->scan_tmp)) return s;
+        hipLaunchKernelGGL(k_starts_to_counts, dim3(1), dim3(1), 0, sm, ss.blocks, nchrom, (uint32_t)nblocks, cc.blocks);
+        hipLaunchKernelGGL(k_block_counts, dim3(1), dim3(1), 0, sm, (const uint32_t *)ss.blocks, (const uint32_t *)cc.blocks, nchrom, (const uint32_t *)h->blk_voff.p,
+                           (const unsigned long long *)h->cfg_base.p, cc.blkvars, cc_cfg);
+        // (phased variants and the blocks whose gwStat text the table does not hold are read with the next wait)
+        const size_t nlist = std::max((size_t)(nblocks + 1) * 2 * nb, NRL) * 4 + 4;          // (0 bytes: a buffer this pass does not use; the pool keeps what an earlier pass grew it to)
+        if (int s = reserve_all(ctx, {{h->labels, NR * 4}, {h->seg_ns, (size_t)(nblocks + 1) * 2 * nb * 4}, {h->big_list, nlist}, {h->big_list2, nlist}, {h->blk_cnt, need_all ? (size_t)(nblocks + 1) * 2 * 4 : 0},
+                                      {h->single_n, nb > 1 || read_ids ? NRL * 4 : 0}, {h->isf0, read_ids ? NR : 0}, {h->isf2, read_ids ? NR : 0}, {h->pool, h->pool.cap ? 0 : (size_t)12 << 20},
+                                      {h->lab_e, (size_t)(nmem + 1) * 2 * nb * 4}, {h->huge_list, ((size_t)(nmem / (STAT_N + 1) + 2) * 2 * (size_t)nb + 16) * 4},
+                                      {h->its, (NR + 1) * 4}, {h->piece_dst, NRL * 8}, {h->big_blk, (size_t)(nblocks + 1) * 4}})) return s;
+        h_cc.assign(lay.n32(), 0u);
+        // ---- read sets of the haplotypes: labels + distinct counts.  No host wait inside: k_seg_small classifies the segments and counts the lists, the wave /
+        //      workgroup kernels take their lists in ticket order and read the counts on the device; the pool-overflow flag is read with the next wait (rare:
+        //      the pool is grown and the stage redone)
+        for (int attempt = 0;; attempt++) {
+            PHZ_HIP(ctx, hipMemsetAsync(h->labels.p, 0, NR * 4, sm));
+            if (read_ids) { PHZ_HIP(ctx, hipMemsetAsync(h->isf0.p, 0, NR, sm)); PHZ_HIP(ctx, hipMemsetAsync(h->isf2.p, 0, NR, sm)); }
+            if (nmem) hipLaunchKernelGGL(k_lab_e, dim3(nblk(nmem * 2 * nb)), dim3(256), 0, sm, nmem, nb, (const uint32_t *)h->mem_s.p, (const uint8_t *)h->v_alle.p, P<uint32_t>(h->lab_e));
+            SG sg; sg.nb = nb; sg.lab_e = P<uint32_t>(h->lab_e); sg.nmem = nmem; sg.mem_s = P<uint32_t>(h->mem_s); sg.blk_mstart = P<uint32_t>(h->blk_mstart); sg.blk_len = P<uint32_t>(h->blk_len); sg.v_alle = P<uint8_t>(h->v_alle);
+            sg.black = h->has_black ? P<uint8_t>(h->d_black) : nullptr; sg.rl_start = T.rl_start; sg.rl_qid = T.rl_qid; sg.labels = P<uint32_t>(h->labels);
+            sg.big_list = P<uint32_t>(h->big_list); sg.big_list2 = P<uint32_t>(h->big_list2); sg.overflow = cnt32 + 20;
+            sg.huge_list = P<uint32_t>(h->huge_list);
+            sg.pool = P<uint32_t>(h->pool); sg.pool_cap = (uint32_t)std::min<size_t>(h->pool.cap / 4, 0xFFFFFFF0u);
+            PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 20, 0, 4, sm));
+            PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 32, 0, 3 * 64, sm));          // every mode has its own counters: [0..3] list lengths / pool cursor, [4] huge segments, [5..7] tickets -- nothing is
+            for (int mode = 0; mode < 3; mode++) {                             // overwritten, so all of it is read back at the ONE wait of the stage
+                if (mode == 1 && !need_all) continue;
+                if (mode == 2 && nb <= 1 && !read_ids) continue;
+                sg.isf = !read_ids ? nullptr : (mode == 0 ? P<uint8_t>(h->isf0) : (mode == 2 ? P<uint8_t>(h->isf2) : nullptr));
+                sg.nseg = mode == 0 ? nblocks * 2 * nb : (mode == 1 ? nblocks * 2 : (int64_t)NRL);
+                sg.ns = mode == 0 ? P<uint32_t>(h->seg_ns) : (mode == 1 ? P<uint32_t>(h->blk_cnt) : P<uint32_t>(h->single_n));
+                if (sg.nseg == 0) continue;
+                uint32_t *mc = cnt32 + 32 + 16 * mode;
+                sg.counters = mc; sg.huge_count = mc + 4; sg.tickets = mc + 5;
+                if (mode == 0) launch_read_sets<0>(sm, sg); else if (mode == 1) launch_read_sets<1>(sm, sg); else launch_read_sets<2>(sm, sg);
             }
+            // ---- text: byte counts -> scan -> write, file by file.  its = scan of the labels' text widths (digits + one separator), the widths computed as the
+            //      scan loads the labels (no width array)
+            if (int s = gscan_excl<uint32_t, uint32_t, LabelWidth>(ctx, P<uint32_t>(h->labels), P<uint32_t>(h->its), n_rl, h->scan_tmp)) return s;
+            PHZ_HIP(ctx, hipMemsetAsync(h->piece_dst.p, 0xff, NRL * 8, sm));
+            if (attempt) PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 12, 0, 4, sm));
+            if (nblocks) hipLaunchKernelGGL(k_big_blocks, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, (const uint32_t *)h->blk_len.p, P<uint32_t>(h->big_blk), cnt32 + 12);
+            PHZ_HIP(ctx, hipGetLastError());
+            PhzMail mail(ctx);
+            const int m_c = mail.add(cnt32, 512), m_ph = mail.add(P<uint32_t>(h->blk_voff) + nblocks, 4), m_cfg = mail.add(P<unsigned long long>(h->cfg_base) + nblocks, 8),
+                      m_cc = mail.add(h->chrom_cnt.p, lay.n32() * 4);
+            (void)mail.add(cc_cfg, (size_t)nchrom * 8);          // (the cfg rows per chromosome travel with the block; no host reader today)
+            if (int s = mail.send()) return s;
+            if (int s = sec.wait("stats + read sets + text sizes")) return s;
+            sec.begin();
+            const uint32_t *hc = mail.at<uint32_t>(m_c);
+            h_nbig = hc[12]; h_nbs = hc[13]; res->phased = (int64_t)*mail.at<uint32_t>(m_ph); h_cfg_total = *mail.at<unsigned long long>(m_cfg);
+            memcpy(h_cc.data(), mail.at<char>(m_cc), lay.n32() * 4);
+            if (!hc[20]) {
+                res->n_big_segments = 0;
+                for (int mode = 0; mode < 3; mode++) res->n_big_segments += (int64_t)hc[32 + 16 * mode] + hc[32 + 16 * mode + 3] + hc[32 + 16 * mode + 4];
+                return PHZ_OK;
+            }
+            if (attempt == 3) return phz_fail(ctx, PHZ_E_NOMEM, "read-set table pool did not converge");
+            if (int s = phz_reserve(ctx, h->pool, h->pool.cap * 4)) return s;           // a segment of more than SEG_LDS reads needs 24 B per read: grow and redo
         }
-        // ---- text: byte counts -> scan -> write, file by file.  its = scan of the labels' text widths (digits + one separator), the widths computed as the
-        //      scan loads the labels (no width array)
-        if (int s = gscan_excl<uint32_t, uint32_t, LabelWidth>(ctx, P<uint32_t>(h->labels), P<uint32_t>(h->its), n_rl, h->scan_tmp)) return s;
-        PHZ_HIP(ctx, hipMemsetAsync(h->piece_dst.p, 0xff, NRL * 8, sm));
-        if (attempt) PHZ_HIP(ctx, hipMemsetAsync(cnt32 + 12, 0, 4, sm));
-        if (nblocks) hipLaunchKernelGGL(k_big_blocks, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, (const uint32_t *)h->blk_len.p, P<uint32_t>(h->big_blk), cnt32 + 12);
-        PHZ_HIP(ctx, hipGetLastError());
-        PhzMail mail(ctx);
-        const int m_c = mail.add(cnt32, 512), m_ph = mail.add(P<uint32_t>(h->blk_voff) + nblocks, 4), m_cfg = mail.add(P<unsigned long long>(h->cfg_base) + nblocks, 8),
-                  m_cc = mail.add(h->chrom_cnt.p, n_cc * 4), m_cfgc = mail.add(cc_cfg, (size_t)nchrom * 8);
-        if (int s = mail.send()) return s;
-        if (int s = sec.wait("stats + read sets + text sizes")) return s;
-        sec.begin();
-        const uint32_t *hc = mail.at<uint32_t>(m_c);
-        h_nbig = hc[12]; h_nbs = hc[13]; h_phased = *mail.at<uint32_t>(m_ph); h_cfg_total = *mail.at<unsigned long long>(m_cfg);
-        memcpy(h_cc.data(), mail.at<char>(m_cc), n_cc * 4); memcpy(h_cfgc.data(), mail.at<char>(m_cfgc), (size_t)nchrom * 8);
-        if (!hc[20]) {
-            res->n_big_segments = 0;
-            for (int mode = 0; mode < 3; mode++) res->n_big_segments += (int64_t)hc[32 + 16 * mode] + hc[32 + 16 * mode + 3] + hc[32 + 16 * mode + 4];
-            break;
+    }
+    // ---- the rows of one file kind: their lengths into rowlen (write = false) or their text at the scanned offsets (true); the rows of big blocks once more, by a wave each
+    template <class ROW, int ROWS, int STAGE, Wave WAVE> void launch_rows_of(int f, bool write) {
+        const unsigned long long *of = P<unsigned long long>(h->off[f]);
+        uint32_t *len = P<uint32_t>(h->rowlen); char *out = P<char>(h->text[f]);
+        if (!write) hipLaunchKernelGGL(k_row_len<ROW>, dim3(nblk(rows[f])), dim3(256), 0, sm, D, rows[f], len);
+        else hipLaunchKernelGGL((k_row_write<ROW, ROWS, STAGE>), dim3((unsigned)((rows[f] + ROWS - 1) / ROWS)), dim3(ROWS), 0, sm, D, rows[f], of, out);
+        if constexpr (WAVE != NO_WAVE) {
+            const int per_blk = WAVE == WAVE_PER_BLOCK_BAM ? nb : 1;
+            if (h_nbig && !write) hipLaunchKernelGGL(k_row_wave_len<ROW>, dim3(h_nbig * (unsigned)per_blk), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, per_blk, len);
+            if (h_nbig && write) hipLaunchKernelGGL(k_row_wave_write<ROW>, dim3(h_nbig * (unsigned)per_blk), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, per_blk, of, out);
         }
-        if (attempt == 3) return phz_fail(ctx, PHZ_E_NOMEM, "read-set table pool did not converge");
-        if (int s = phz_reserve(ctx, h->pool, h->pool.cap * 4)) return s;           // a segment of more than SEG_LDS reads needs 24 B per read: grow and redo
     }
-    res->phased = (int64_t)h_phased;
-    // gwStat text the table does not hold -- blocks with more known phases than it covers (:968-980), and with --gw_phase_method 1 every block phased by MAF weight (:1002) --: repr() of the float64 the device computed
-    if (h_nbs) {
-        std::string xt; std::vector<uint32_t> xo((size_t)h_nbs + 1, 0u); std::vector<double> bsv((size_t)h_nbs);
-        PHZ_HIP(ctx, hipMemcpy(bsv.data(), h->big_stat.p, bsv.size() * 8, hipMemcpyDeviceToHost));
-        xt.reserve((size_t)h_nbs * 20);
-        for (uint32_t i = 0; i < h_nbs; i++) {
-            xo[i] = (uint32_t)xt.size();
-            phztext::put_pyfloat(xt, bsv[i]);
-            xt += '\n';
+    void launch_rows(int f, bool write) {
+        if (!rows[f]) return;
+        switch (f) {
+            case PHZ_TXT_CONN: return launch_rows_of<RowConn, 256, 24 * 1024, NO_WAVE>(f, write);
+            case PHZ_TXT_HAP: return launch_rows_of<RowHap, PHZ_HAP_ROWS, PHZ_HAP_STAGE, WAVE_PER_BLOCK>(f, write);
+            case PHZ_TXT_ASE: return launch_rows_of<RowAse, PHZ_ASE_ROWS, PHZ_ASE_STAGE, WAVE_PER_BLOCK_BAM>(f, write);
+            case PHZ_TXT_ALLELIC: return launch_rows_of<RowAllelic, 256, 24 * 1024, NO_WAVE>(f, write);
+            case PHZ_TXT_SINGLE_ASE: return launch_rows_of<RowSingleAse, 256, 32 * 1024, NO_WAVE>(f, write);
+            case PHZ_TXT_SINGLE_HAP: return launch_rows_of<RowSingleHap, 256, 32 * 1024, NO_WAVE>(f, write);
+            default:          // allele_config: no length pass (its offsets come in closed form, k_cfg_prefix)
+                if (write) hipLaunchKernelGGL((k_cfg_write<128, 12 * 1024>), dim3((unsigned)((rows[f] + 127) / 128)), dim3(128), 0, sm, D, rows[f], P<char>(h->text[f]));
         }
-        xo[h_nbs] = (uint32_t)xt.size();
-        if (int s = up(ctx, h->px_off, xo.data(), xo.size() * 4)) return s;
-        if (int s = up(ctx, h->px_txt, xt.data(), xt.size())) return s;
-        PHZ_HIP(ctx, hipStreamSynchronize(sm));            // xo / xt die with this scope
     }
-    const uint32_t *blk_cnt = need_all ? P<uint32_t>(h->blk_cnt) : P<uint32_t>(h->seg_ns);     // one BAM, nothing blacklisted: the two read sets coincide
-    if (n_rl * 12 >= (1ll << 32)) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "device row stage: read-label text beyond 4 GiB");
-    RD D; memset(&D, 0, sizeof(D));
-    D.nv = nv; D.ne = ne; D.nblocks = nblocks; D.n_linked = n_linked; D.n_keys = nkeys; D.nchrom = nchrom; D.nb = nb; D.unique_ids = o->unique_ids; D.unphased_vars = o->unphased_vars;
-    D.vchrom = P<uint16_t>(h->d_vchrom); D.pos = P<int32_t>(h->d_pos);
-    auto pool = [&](int i) { PoolD p; p.off = P<uint32_t>(h->p_off[i]); p.b = P<char>(h->p_txt[i]); return p; };
-    D.uid = pool(0); D.rsid = pool(1); D.alle = pool(2); D.maft = pool(3); D.chromn = pool(4); D.statt = pool(5);
-    D.statx.off = P<uint32_t>(h->px_off); D.statx.b = P<char>(h->px_txt);
-    D.bamn.off = d_bam_off; D.bamn.b = d_bam_txt; D.pvt.off = d_pv_off; D.pvt.b = d_pv_txt;
-    D.mafv = P<double>(h->d_maf); D.is_ref = P<uint8_t>(h->d_isref); D.phase_idx = P<int8_t>(h->d_phase); D.black = h->has_black ? P<uint8_t>(h->d_black) : nullptr;
-    D.bam_excl = o->bam_excluded ? d_bam_excl : nullptr;
-    D.var_count = T.var_count; D.var_distinct = T.var_distinct; D.ea = T.ea; D.eb = T.eb; D.cis = cis; D.trans = trans; D.sup = sup; D.tot = tot; D.cfgv = cfgv;
-    D.rl_start = T.rl_start; D.rl_qid = T.rl_qid; D.rl_list = T.rl_list;
-    D.eorder = P<uint32_t>(h->eorder); D.va = P<int32_t>(h->va); D.vb = P<int32_t>(h->vb); D.e_slot = P<uint32_t>(h->e_slot); D.key_g = P<uint32_t>(h->key_g);
-    D.mem_s = P<uint32_t>(h->mem_s); D.blk_mstart = P<uint32_t>(h->blk_mstart); D.blk_len = P<uint32_t>(h->blk_len); D.blk_of = P<int32_t>(h->blk_of); D.v_alle = P<uint8_t>(h->v_alle);
-    D.blk_sup = P<uint32_t>(h->blk_sup); D.blk_tot = P<uint32_t>(h->blk_tot); D.blk_cnt = blk_cnt; D.seg_ns = P<uint32_t>(h->seg_ns); D.single_n = nb > 1 ? P<uint32_t>(h->single_n) : nullptr;
-    D.blk_conc = P<uint8_t>(h->conc); D.blk_cormode = P<uint8_t>(h->cormode); D.blk_statkind = P<uint8_t>(h->statkind); D.blk_statidx = P<uint32_t>(h->statidx);
-    D.blk_maxmaf = P<int32_t>(h->maxmaf); D.its = P<uint32_t>(h->its); D.labels = P<uint32_t>(h->labels); D.piece_dst = P<unsigned long long>(h->piece_dst);
-    D.cfg_base = P<unsigned long long>(h->cfg_base);
-    D.nmem = nmem;
-    D.read_ids = read_ids ? 1 : 0;
-    if (read_ids) { D.qn.off = P<uint32_t>(h->qn_off); D.qn.b = P<char>(h->qn_txt); D.qbase = P<long long>(h->qn_base); D.isf0 = P<uint8_t>(h->isf0); D.isf2 = P<uint8_t>(h->isf2); }
-    RSV(mrec, (size_t)(nmem + 1) * sizeof(MemRec)); RSV(lab_e, (size_t)(nmem + 1) * 2 * nb * 4); RSV(lab_skip, (size_t)(nmem + 1) * 2 * nb * 4);
-    D.mrec = P<MemRec>(h->mrec); D.lab_e = P<uint32_t>(h->lab_e); D.lab_skip = P<uint32_t>(h->lab_skip);
-    if (nmem) {
-        hipLaunchKernelGGL(k_mem_rec, dim3(nblk(nmem)), dim3(256), 0, sm, D, P<MemRec>(h->mrec));
-        hipLaunchKernelGGL(k_mem_lab, dim3(nblk(nmem * 2 * nb)), dim3(256), 0, sm, D, P<uint32_t>(h->lab_e), P<uint32_t>(h->lab_skip));
-    }
-    {
+    // ---- row lengths, their scans, and the byte offsets of the per-chromosome segments
+    int text_byte_offsets() {
+        // gwStat text the table does not hold -- blocks with more known phases than it covers (:968-980), and with --gw_phase_method 1 every block phased by MAF weight (:1002) --: repr() of the float64 the device computed
+        if (h_nbs) {
+            std::string xt; std::vector<uint32_t> xo((size_t)h_nbs + 1, 0u); std::vector<double> bsv((size_t)h_nbs);
+            PHZ_HIP(ctx, hipMemcpy(bsv.data(), h->big_stat.p, bsv.size() * 8, hipMemcpyDeviceToHost));
+            xt.reserve((size_t)h_nbs * 20);
+            for (uint32_t i = 0; i < h_nbs; i++) {
+                xo[i] = (uint32_t)xt.size();
+                phztext::put_pyfloat(xt, bsv[i]);
+                xt += '\n';
+            }
+            xo[h_nbs] = (uint32_t)xt.size();
+            if (int s = up(ctx, h->px_off, xo.data(), xo.size() * 4)) return s;
+            if (int s = up(ctx, h->px_txt, xt.data(), xt.size())) return s;
+            PHZ_HIP(ctx, hipStreamSynchronize(sm));            // xo / xt die with this scope
+        }
+        if (n_rl * 12 >= (1ll << 32)) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "device row stage: read-label text beyond 4 GiB");
+        // ---- everything the row functions read, and the per-member records / prefix arrays built from it
+        const uint32_t *blk_cnt = need_all ? P<uint32_t>(h->blk_cnt) : P<uint32_t>(h->seg_ns);     // one BAM, nothing blacklisted: the two read sets coincide
+        memset(&D, 0, sizeof(D));
+        D.nv = nv; D.ne = ne; D.nblocks = nblocks; D.n_linked = n_linked; D.n_keys = nkeys; D.nchrom = nchrom; D.nb = nb; D.unique_ids = o->unique_ids; D.unphased_vars = o->unphased_vars;
+        D.vchrom = P<uint16_t>(h->d_vchrom); D.pos = P<int32_t>(h->d_pos);
+        auto pool = [&](int i) { PoolD p; p.off = P<uint32_t>(h->p_off[i]); p.b = P<char>(h->p_txt[i]); return p; };
+        D.uid = pool(0); D.rsid = pool(1); D.alle = pool(2); D.maft = pool(3); D.chromn = pool(4); D.statt = pool(5);
+        D.statx.off = P<uint32_t>(h->px_off); D.statx.b = P<char>(h->px_txt);
+        D.bamn.off = d_bam_off; D.bamn.b = d_bam_txt; D.pvt.off = d_pv_off; D.pvt.b = d_pv_txt;
+        D.mafv = P<double>(h->d_maf); D.is_ref = P<uint8_t>(h->d_isref); D.phase_idx = P<int8_t>(h->d_phase); D.black = h->has_black ? P<uint8_t>(h->d_black) : nullptr;
+        D.bam_excl = o->bam_excluded ? d_bam_excl : nullptr;
+        D.var_count = T.var_count; D.var_distinct = T.var_distinct; D.ea = T.ea; D.eb = T.eb; D.cis = cis; D.trans = trans; D.sup = sup; D.tot = tot; D.cfgv = cfgv;
+        D.rl_start = T.rl_start; D.rl_qid = T.rl_qid; D.rl_list = T.rl_list;
+        D.eorder = P<uint32_t>(h->eorder); D.va = P<int32_t>(h->va); D.vb = P<int32_t>(h->vb); D.e_slot = P<uint32_t>(h->e_slot); D.key_g = P<uint32_t>(h->key_g);
+        D.mem_s = P<uint32_t>(h->mem_s); D.blk_mstart = P<uint32_t>(h->blk_mstart); D.blk_len = P<uint32_t>(h->blk_len); D.blk_of = P<int32_t>(h->blk_of); D.v_alle = P<uint8_t>(h->v_alle);
+        D.blk_sup = P<uint32_t>(h->blk_sup); D.blk_tot = P<uint32_t>(h->blk_tot); D.blk_cnt = blk_cnt; D.seg_ns = P<uint32_t>(h->seg_ns); D.single_n = nb > 1 ? P<uint32_t>(h->single_n) : nullptr;
+        D.blk_conc = P<uint8_t>(h->conc); D.blk_cormode = P<uint8_t>(h->cormode); D.blk_statkind = P<uint8_t>(h->statkind); D.blk_statidx = P<uint32_t>(h->statidx);
+        D.blk_maxmaf = P<int32_t>(h->maxmaf); D.its = P<uint32_t>(h->its); D.labels = P<uint32_t>(h->labels); D.piece_dst = P<unsigned long long>(h->piece_dst);
+        D.cfg_base = P<unsigned long long>(h->cfg_base);
+        D.nmem = nmem;
+        D.read_ids = read_ids ? 1 : 0;
+        if (read_ids) { D.qn.off = P<uint32_t>(h->qn_off); D.qn.b = P<char>(h->qn_txt); D.qbase = P<long long>(h->qn_base); D.isf0 = P<uint8_t>(h->isf0); D.isf2 = P<uint8_t>(h->isf2); }
         const int64_t nchunks = ((int64_t)h_cfg_total + 255) / 256;
-        RSV(cfg_chunk, (size_t)(nchunks + 1) * 4);
+        if (int s = reserve_all(ctx, {{h->mrec, (size_t)(nmem + 1) * sizeof(MemRec)}, {h->lab_skip, (size_t)(nmem + 1) * 2 * nb * 4}, {h->cfg_chunk, (size_t)(nchunks + 1) * 4}, {h->cfg_pl, (size_t)(nmem + 1) * 4},
+                                      {h->cfg_pb, (size_t)(nmem + 1) * 4}, {h->cfg_ps, (size_t)(nmem + 1) * 8}, {h->cfg_bytes, (size_t)(nblocks + 1) * 8}, {h->cfg_bbase, (size_t)(nblocks + 2) * 8}})) return s;
+        D.mrec = P<MemRec>(h->mrec); D.lab_e = P<uint32_t>(h->lab_e); D.lab_skip = P<uint32_t>(h->lab_skip);
+        if (nmem) {
+            hipLaunchKernelGGL(k_mem_rec, dim3(nblk(nmem)), dim3(256), 0, sm, D, P<MemRec>(h->mrec));
+            hipLaunchKernelGGL(k_mem_lab, dim3(nblk(nmem * 2 * nb)), dim3(256), 0, sm, D, P<uint32_t>(h->lab_e), P<uint32_t>(h->lab_skip));
+        }
         if (nchunks) hipLaunchKernelGGL(k_cfg_chunks, dim3(nblk(nchunks)), dim3(256), 0, sm, nchunks, nblocks, (const unsigned long long *)h->cfg_base.p, P<uint32_t>(h->cfg_chunk));
         D.cfg_chunk = P<uint32_t>(h->cfg_chunk);
-    }
-    // allele_config offsets in closed form: prefix arrays per block member, bytes per block, one scan over the blocks (not over the rows)
-    RSV(cfg_pl, (size_t)(nmem + 1) * 4); RSV(cfg_pb, (size_t)(nmem + 1) * 4); RSV(cfg_ps, (size_t)(nmem + 1) * 8); RSV(cfg_bytes, (size_t)(nblocks + 1) * 8); RSV(cfg_bbase, (size_t)(nblocks + 2) * 8);
-    D.cfg_pl = P<uint32_t>(h->cfg_pl); D.cfg_pb = P<uint32_t>(h->cfg_pb); D.cfg_ps = P<unsigned long long>(h->cfg_ps); D.cfg_bbase = P<unsigned long long>(h->cfg_bbase);
-    if (nblocks) hipLaunchKernelGGL(k_cfg_prefix, dim3(nblk(nblocks)), dim3(256), 0, sm, D, nblocks, P<uint32_t>(h->cfg_pl), P<uint32_t>(h->cfg_pb), P<unsigned long long>(h->cfg_ps),
-                                    P<unsigned long long>(h->cfg_bytes));
-    if (h_nbig) hipLaunchKernelGGL(k_cfg_prefix_wave, dim3(h_nbig), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, P<uint32_t>(h->cfg_pl), P<uint32_t>(h->cfg_pb),
-                                   P<unsigned long long>(h->cfg_ps), P<unsigned long long>(h->cfg_bytes));
-    if (int s = gscan_excl<unsigned long long, unsigned long long>(ctx, P<unsigned long long>(h->cfg_bytes), P<unsigned long long>(h->cfg_bbase), nblocks, h->scan_tmp)) return s;
-    const int64_t rows[PHZ_TXT_COUNT] = {n_linked, nblocks, nblocks * nb, (int64_t)h_cfg_total, nkeys, nkeys * nb, nkeys};
-    int64_t max_rows = 1;
-    for (int f = 0; f < PHZ_TXT_COUNT; f++) max_rows = std::max(max_rows, rows[f]);
-    RSV(rowlen, (size_t)max_rows * 4);
-    // per-file segment tables: rows per chromosome (per BAM x chromosome for the key files), prefix-summed on the device into byte offsets
-    const int nseg[PHZ_TXT_COUNT] = {nchrom, nchrom, nchrom, nchrom, nb * nchrom, nb * nchrom, nb * nchrom};
-    uint32_t *d_nb = cnt32 + 8;
-    hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, d_nb, (int64_t)1, (uint32_t)nb);
-    for (int f = 0; f < PHZ_TXT_COUNT; f++) {
-        RSV(seg_off_d[f], (size_t)(nseg[f] + 1) * 8);
-        if (f == PHZ_TXT_CFG) {        // offsets in closed form: per-chromosome byte offsets = the byte base of the chromosome's first block
-            hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_blocks, (const uint32_t *)nullptr, nseg[f], (const unsigned long long *)h->cfg_bbase.p,
+        // allele_config offsets in closed form: prefix arrays per block member, bytes per block, one scan over the blocks (not over the rows)
+        D.cfg_pl = P<uint32_t>(h->cfg_pl); D.cfg_pb = P<uint32_t>(h->cfg_pb); D.cfg_ps = P<unsigned long long>(h->cfg_ps); D.cfg_bbase = P<unsigned long long>(h->cfg_bbase);
+        if (nblocks) hipLaunchKernelGGL(k_cfg_prefix, dim3(nblk(nblocks)), dim3(256), 0, sm, D, nblocks, P<uint32_t>(h->cfg_pl), P<uint32_t>(h->cfg_pb), P<unsigned long long>(h->cfg_ps),
+                                        P<unsigned long long>(h->cfg_bytes));
+        if (h_nbig) hipLaunchKernelGGL(k_cfg_prefix_wave, dim3(h_nbig), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, P<uint32_t>(h->cfg_pl), P<uint32_t>(h->cfg_pb),
+                                       P<unsigned long long>(h->cfg_ps), P<unsigned long long>(h->cfg_bytes));
+        if (int s = gscan_excl<unsigned long long, unsigned long long>(ctx, P<unsigned long long>(h->cfg_bytes), P<unsigned long long>(h->cfg_bbase), nblocks, h->scan_tmp)) return s;
+        const int64_t file_rows[PHZ_TXT_COUNT] = {n_linked, nblocks, nblocks * nb, (int64_t)h_cfg_total, nkeys, nkeys * nb, nkeys};
+        memcpy(rows, file_rows, sizeof(rows));
+        const int64_t max_rows = std::max<int64_t>(1, *std::max_element(rows, rows + PHZ_TXT_COUNT));
+        if (int s = phz_reserve(ctx, h->rowlen, (size_t)max_rows * 4)) return s;
+        // per-file segment tables: rows per chromosome (per BAM x chromosome for the key files), prefix-summed on the device into byte offsets
+        uint32_t *d_nb = cnt32 + 8;
+        hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, sm, d_nb, (int64_t)1, (uint32_t)nb);
+        for (int f = 0; f < PHZ_TXT_COUNT; f++) {
+            if (int s = phz_reserve(ctx, h->seg_off_d[f], (size_t)(seg_count(f) + 1) * 8)) return s;
+            const unsigned long long *of = P<unsigned long long>(h->cfg_bbase);        // allele_config, offsets in closed form: per-chromosome byte offsets = the byte base of the chromosome's first block
+            if (f != PHZ_TXT_CFG) {
+                if (int s = phz_reserve(ctx, h->off[f], (size_t)(rows[f] + 1) * 8)) return s;
+                uint32_t *len = P<uint32_t>(h->rowlen);
+                launch_rows(f, false);
+                if (f == PHZ_TXT_ALLELIC && rows[f]) hipLaunchKernelGGL(k_count_nonzero, dim3(std::min(nblk(rows[f]), 512u)), dim3(256), 0, sm, (const uint32_t *)len, rows[f], cnt64 + 4);
+                if (int s = gscan_excl<uint32_t, unsigned long long>(ctx, len, P<unsigned long long>(h->off[f]), rows[f], h->scan_tmp)) return s;
+                of = P<unsigned long long>(h->off[f]);
+            }
+            hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)(cc.*SEG_ROWS[f].count), (const uint32_t *)(SEG_ROWS[f].times_bams ? d_nb : nullptr), seg_count(f), of,
                                P<unsigned long long>(h->seg_off_d[f]));
-            continue;
         }
-        RSV(off[f], (size_t)(rows[f] + 1) * 8);
-        const unsigned g = nblk(rows[f]);
-        uint32_t *len = P<uint32_t>(h->rowlen);
-        if (rows[f]) switch (f) {
-            case PHZ_TXT_CONN: hipLaunchKernelGGL(k_row_len<RowConn>, dim3(g), dim3(256), 0, sm, D, rows[f], len); break;
-            case PHZ_TXT_HAP: hipLaunchKernelGGL(k_row_len<RowHap>, dim3(g), dim3(256), 0, sm, D, rows[f], len);
-                if (h_nbig) hipLaunchKernelGGL(k_row_wave_len<RowHap>, dim3(h_nbig), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, 1, len);
-                break;
-            case PHZ_TXT_ASE: hipLaunchKernelGGL(k_row_len<RowAse>, dim3(g), dim3(256), 0, sm, D, rows[f], len);
-                if (h_nbig) hipLaunchKernelGGL(k_row_wave_len<RowAse>, dim3(h_nbig * (unsigned)nb), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, nb, len);
-                break;
-            case PHZ_TXT_ALLELIC: hipLaunchKernelGGL(k_row_len<RowAllelic>, dim3(g), dim3(256), 0, sm, D, rows[f], len); break;
-            case PHZ_TXT_SINGLE_ASE: hipLaunchKernelGGL(k_row_len<RowSingleAse>, dim3(g), dim3(256), 0, sm, D, rows[f], len); break;
-            default: hipLaunchKernelGGL(k_row_len<RowSingleHap>, dim3(g), dim3(256), 0, sm, D, rows[f], len); break;
-        }
-        if (f == PHZ_TXT_ALLELIC && rows[f]) hipLaunchKernelGGL(k_count_nonzero, dim3(g < 512u ? g : 512u), dim3(256), 0, sm, (const uint32_t *)len, rows[f], cnt64 + 4);
-        if (int s = gscan_excl<uint32_t, unsigned long long>(ctx, len, P<unsigned long long>(h->off[f]), rows[f], h->scan_tmp)) return s;
-        unsigned long long *so = P<unsigned long long>(h->seg_off_d[f]);
-        const unsigned long long *of = P<unsigned long long>(h->off[f]);
-        switch (f) {
-            case PHZ_TXT_CONN: hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_conn, (const uint32_t *)nullptr, nseg[f], of, so); break;
-            case PHZ_TXT_HAP: hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_blocks, (const uint32_t *)nullptr, nseg[f], of, so); break;
-            case PHZ_TXT_ASE: hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_blocks, (const uint32_t *)d_nb, nseg[f], of, so); break;
-            case PHZ_TXT_SINGLE_ASE: hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_keys, (const uint32_t *)d_nb, nseg[f], of, so); break;
-            default: hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, sm, (const uint32_t *)cc_keys, (const uint32_t *)nullptr, nseg[f], of, so); break;
-        }
-    }
-    PHZ_HIP(ctx, hipGetLastError());
-    std::vector<unsigned long long> h_so[PHZ_TXT_COUNT];
-    {
+        PHZ_HIP(ctx, hipGetLastError());
         PhzMail mail(ctx);
         int m_so[PHZ_TXT_COUNT];
         const int m_az = mail.add(cnt64 + 4, 8);
-        for (int f = 0; f < PHZ_TXT_COUNT; f++) m_so[f] = mail.add(h->seg_off_d[f].p, ((size_t)nseg[f] + 1) * 8);
+        for (int f = 0; f < PHZ_TXT_COUNT; f++) m_so[f] = mail.add(h->seg_off_d[f].p, ((size_t)seg_count(f) + 1) * 8);
         if (int s = mail.send()) return s;
         if (int s = sec.wait("text: byte offsets")) return s;
-        h_c64[4] = *mail.at<unsigned long long>(m_az);
-        for (int f = 0; f < PHZ_TXT_COUNT; f++) { const unsigned long long *q = mail.at<unsigned long long>(m_so[f]); h_so[f].assign(q, q + (size_t)nseg[f] + 1); }
-    }
-    sec.begin();
-    // Where the text goes on the host, when the caller gave a page-locked region that holds all of it (phz_rowsdev_opts.host_text): every file at a 4 KB boundary, copied
-    // on the ctx's copy stream AS SOON AS ITS WRITER HAS FINISHED -- largest file first (allele_config is half of the bytes), so that the link is busy from the first
-    // finished file on while the other writers still run.  (The files are all written in the last fifth of a pass: what this hides is that fifth, not the pass.)
-    bool to_host = o->host_text != nullptr && o->host_text_cap > 0;
-    struct CopyGuard {          // whatever way this call ends, no copy into the caller's region is still in flight when it returns
-        phz_ctx *c; bool armed = false;
-        ~CopyGuard() { if (armed && c->copy_stream) (void)hipStreamSynchronize(c->copy_stream); }
-    } copy_guard{ctx};
-    int64_t host_need = 0;
-    for (int f = 0; f < PHZ_TXT_COUNT; f++) {
-        h->bytes[f] = (int64_t)h_so[f].back();
-        h->seg_off[f].assign(h_so[f].begin(), h_so[f].end());
-        res->bytes[f] = h->bytes[f]; res->seg_off[f] = h->seg_off[f].data();
-        res->host_off[f] = -1;
-        host_need = ((host_need + 4095) & ~(int64_t)4095) + h->bytes[f];
-    }
-    if (to_host && host_need > o->host_text_cap) to_host = false;
-    if (to_host) {
-        if (!ctx->copy_stream) PHZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        int64_t at = 0;
-        for (int f = 0; f < PHZ_TXT_COUNT; f++) { at = (at + 4095) & ~(int64_t)4095; res->host_off[f] = at; at += h->bytes[f]; }
-        for (int f = 0; f < PHZ_TXT_COUNT; f++) if (!h->txt_ev[f]) PHZ_HIP(ctx, hipEventCreateWithFlags(&h->txt_ev[f], hipEventDisableTiming));
-    }
-    static const int write_order[PHZ_TXT_COUNT] = {PHZ_TXT_CFG, PHZ_TXT_ASE, PHZ_TXT_ALLELIC, PHZ_TXT_CONN, PHZ_TXT_HAP, PHZ_TXT_SINGLE_ASE, PHZ_TXT_SINGLE_HAP};
-    for (int wo = 0; wo < PHZ_TXT_COUNT; wo++) {
-        const int f = write_order[wo];
-        RSV(text[f], (size_t)h->bytes[f] + 16);
-        const unsigned g = nblk(rows[f]);
-        const unsigned long long *of = P<unsigned long long>(h->off[f]);
-        char *out = P<char>(h->text[f]);
-        if (rows[f]) switch (f) {
-            case PHZ_TXT_CONN: hipLaunchKernelGGL((k_row_write<RowConn, 256, 24 * 1024>), dim3((unsigned)((rows[f] + 255) / 256)), dim3(256), 0, sm, D, rows[f], of, out); break;
-            case PHZ_TXT_HAP: hipLaunchKernelGGL((k_row_write<RowHap, PHZ_HAP_ROWS, PHZ_HAP_STAGE>), dim3((unsigned)((rows[f] + PHZ_HAP_ROWS - 1) / PHZ_HAP_ROWS)), dim3(PHZ_HAP_ROWS), 0, sm, D, rows[f], of, out);
-                if (h_nbig) hipLaunchKernelGGL(k_row_wave_write<RowHap>, dim3(h_nbig), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, 1, of, out);
-                break;
-            case PHZ_TXT_ASE: hipLaunchKernelGGL((k_row_write<RowAse, PHZ_ASE_ROWS, PHZ_ASE_STAGE>), dim3((unsigned)((rows[f] + PHZ_ASE_ROWS - 1) / PHZ_ASE_ROWS)), dim3(PHZ_ASE_ROWS), 0, sm, D, rows[f], of, out);
-                if (h_nbig) hipLaunchKernelGGL(k_row_wave_write<RowAse>, dim3(h_nbig * (unsigned)nb), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, nb, of, out);
-                break;
-            case PHZ_TXT_CFG: hipLaunchKernelGGL((k_cfg_write<128, 12 * 1024>), dim3((unsigned)((rows[f] + 127) / 128)), dim3(128), 0, sm, D, rows[f], out); break;
-            case PHZ_TXT_ALLELIC: hipLaunchKernelGGL((k_row_write<RowAllelic, 256, 24 * 1024>), dim3((unsigned)((rows[f] + 255) / 256)), dim3(256), 0, sm, D, rows[f], of, out); break;
-            case PHZ_TXT_SINGLE_ASE: hipLaunchKernelGGL((k_row_write<RowSingleAse, 256, 32 * 1024>), dim3((unsigned)((rows[f] + 255) / 256)), dim3(256), 0, sm, D, rows[f], of, out); break;
-            default: hipLaunchKernelGGL((k_row_write<RowSingleHap, 256, 32 * 1024>), dim3((unsigned)((rows[f] + 255) / 256)), dim3(256), 0, sm, D, rows[f], of, out); break;
+        res->allelic_rows = (int64_t)*mail.at<unsigned long long>(m_az);
+        for (int f = 0; f < PHZ_TXT_COUNT; f++) {
+            const unsigned long long *q = mail.at<unsigned long long>(m_so[f]);
+            h->seg_off[f].assign(q, q + (size_t)seg_count(f) + 1);
+            h->bytes[f] = (int64_t)q[seg_count(f)];
         }
-        if (f == PHZ_TXT_ASE && n_rl && rows[f]) hipLaunchKernelGGL(k_label_write, dim3(nblk(n_rl)), dim3(256), 0, sm, D, n_rl, out);
-        if (to_host && h->bytes[f]) {
-            PHZ_HIP(ctx, hipEventRecord(h->txt_ev[f], sm));
-            PHZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, h->txt_ev[f], 0));
-            copy_guard.armed = true;
-            PHZ_HIP(ctx, hipMemcpyAsync((char *)o->host_text + res->host_off[f], h->text[f].p, (size_t)h->bytes[f], hipMemcpyDeviceToHost, ctx->copy_stream));
+        sec.begin();
+        return PHZ_OK;
+    }
+    // ---- the writers, each file copied to the host as soon as it is written, and the per-block arrays of write_vcf
+    int write_text() {
+        // Where the text goes on the host, when the caller gave a page-locked region that holds all of it (phz_rowsdev_opts.host_text): every file at a 4 KB boundary, copied
+        // on the ctx's copy stream AS SOON AS ITS WRITER HAS FINISHED -- largest file first (allele_config is half of the bytes), so that the link is busy from the first
+        // finished file on while the other writers still run.  (The files are all written in the last fifth of a pass: what this hides is that fifth, not the pass.)
+        bool to_host = o->host_text != nullptr && o->host_text_cap > 0;
+        int64_t host_need = 0;
+        for (int f = 0; f < PHZ_TXT_COUNT; f++) {
+            res->bytes[f] = h->bytes[f]; res->seg_off[f] = h->seg_off[f].data();
+            res->host_off[f] = -1;
+            host_need = ((host_need + 4095) & ~(int64_t)4095) + h->bytes[f];
         }
+        if (to_host && host_need > o->host_text_cap) to_host = false;
+        if (to_host) {
+            if (!ctx->copy_stream) PHZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+            int64_t at = 0;
+            for (int f = 0; f < PHZ_TXT_COUNT; f++) { at = (at + 4095) & ~(int64_t)4095; res->host_off[f] = at; at += h->bytes[f]; }
+            for (int f = 0; f < PHZ_TXT_COUNT; f++) if (!h->txt_ev[f]) PHZ_HIP(ctx, hipEventCreateWithFlags(&h->txt_ev[f], hipEventDisableTiming));
+        }
+        for (int wo = 0; wo < PHZ_TXT_COUNT; wo++) {
+            const int f = WRITE_ORDER[wo];
+            if (int s = phz_reserve(ctx, h->text[f], (size_t)h->bytes[f] + 16)) return s;
+            launch_rows(f, true);
+            if (f == PHZ_TXT_ASE && n_rl && rows[f]) hipLaunchKernelGGL(k_label_write, dim3(nblk(n_rl)), dim3(256), 0, sm, D, n_rl, P<char>(h->text[f]));
+            if (to_host && h->bytes[f]) {
+                PHZ_HIP(ctx, hipEventRecord(h->txt_ev[f], sm));
+                PHZ_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, h->txt_ev[f], 0));
+                copy_guard.armed = true;
+                PHZ_HIP(ctx, hipMemcpyAsync((char *)o->host_text + res->host_off[f], h->text[f].p, (size_t)h->bytes[f], hipMemcpyDeviceToHost, ctx->copy_stream));
+            }
+        }
+        // ---- per-block arrays for write_vcf
+        h->have_vcf = false;
+        h->n_blocks = nblocks; h->n_blk_vars = res->phased;
+        if (o->want_vcf && nblocks) {
+            if (int s = reserve_all(ctx, {{h->o_var, (size_t)(res->phased + 1) * 4}, {h->o_maxmaf, (size_t)(nblocks + 1) * 4}, {h->o_hap, (size_t)(res->phased + 1)},
+                                          {h->o_cor, (size_t)(res->phased + 1) * 2}})) return s;
+            VB vbk; vbk.mem_s = P<uint32_t>(h->mem_s); vbk.blk_mstart = P<uint32_t>(h->blk_mstart); vbk.blk_len = P<uint32_t>(h->blk_len); vbk.blk_voff = P<uint32_t>(h->blk_voff);
+            vbk.v_alle = P<uint8_t>(h->v_alle); vbk.cormode = P<uint8_t>(h->cormode); vbk.phase_idx = P<int8_t>(h->d_phase); vbk.maxmaf = P<int32_t>(h->maxmaf);
+            vbk.vchrom = P<uint16_t>(h->d_vchrom); vbk.chrom_v0 = (const long long *)h->d_chrom_v0.p; vbk.o_var = P<int32_t>(h->o_var); vbk.o_maxmaf = P<int32_t>(h->o_maxmaf);
+            vbk.o_hap = P<uint8_t>(h->o_hap); vbk.o_cor = P<int8_t>(h->o_cor);
+            hipLaunchKernelGGL(k_vcf_blocks, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, vbk);
+            h->have_vcf = true;
+        }
+        PHZ_HIP(ctx, hipGetLastError());
+        if (int s = sec.wait("end")) return s;
+        if (to_host) { copy_guard.armed = false; PHZ_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); }          // the text is in the caller's region
+        return PHZ_OK;
     }
-    // ---- per-block arrays for write_vcf
-    h->have_vcf = false;
-    h->n_blocks = nblocks; h->n_blk_vars = res->phased;
-    if (o->want_vcf && nblocks) {
-        RSV(o_var, (size_t)(res->phased + 1) * 4); RSV(o_maxmaf, (size_t)(nblocks + 1) * 4); RSV(o_hap, (size_t)(res->phased + 1)); RSV(o_cor, (size_t)(res->phased + 1) * 2);
-        VB vbk; vbk.mem_s = P<uint32_t>(h->mem_s); vbk.blk_mstart = P<uint32_t>(h->blk_mstart); vbk.blk_len = P<uint32_t>(h->blk_len); vbk.blk_voff = P<uint32_t>(h->blk_voff);
-        vbk.v_alle = P<uint8_t>(h->v_alle); vbk.cormode = P<uint8_t>(h->cormode); vbk.phase_idx = P<int8_t>(h->d_phase); vbk.maxmaf = P<int32_t>(h->maxmaf);
-        vbk.vchrom = P<uint16_t>(h->d_vchrom); vbk.chrom_v0 = (const long long *)h->d_chrom_v0.p; vbk.o_var = P<int32_t>(h->o_var); vbk.o_maxmaf = P<int32_t>(h->o_maxmaf);
-        vbk.o_hap = P<uint8_t>(h->o_hap); vbk.o_cor = P<int8_t>(h->o_cor);
-        hipLaunchKernelGGL(k_vcf_blocks, dim3(nblk(nblocks)), dim3(256), 0, sm, nblocks, vbk);
-        h->have_vcf = true;
+    void publish() {
+        const ChromTab hc = lay.tab(h_cc.data());
+        h->chrom_blocks.assign(hc.blocks, hc.blocks + nchrom); h->chrom_blk_vars.assign(hc.blkvars, hc.blkvars + nchrom);
+        res->chrom_blocks = h->chrom_blocks.data(); res->chrom_blk_vars = h->chrom_blk_vars.data();
+        // the reference orders the chromosomes of the block files by the first BAM whose call file has a kept line on them (read_vars is keyed by the `chrom` that
+        // process_mapping_result returns, "" for a file without kept lines: phaser.py:1299, :573-574), VCF order inside a BAM.  A chromosome's covered variants are
+        // counted per (BAM of the first kept line, chromosome): its first BAM is the first of those counters that is not zero.
+        h->chrom_first_bam.assign((size_t)nchrom, -1);
+        for (int c = 0; c < nchrom; c++)
+            for (int b = 0; b < nb; b++)
+                if (hc.keys[(size_t)b * nchrom + c]) { h->chrom_first_bam[(size_t)c] = b; break; }
+        res->chrom_first_bam = h->chrom_first_bam.data();
+        res->n_blocks = nblocks; res->n_blk_vars = res->phased; res->n_components = ncomp; res->n_linked = n_linked;
+        res->gpu_ms = sec.ms;
+        ctx->last_ms[PHZ_T_ROWS] = (float)sec.ms; ctx->total_ms[PHZ_T_ROWS] += sec.ms; ctx->launches[PHZ_T_ROWS]++;
     }
-    PHZ_HIP(ctx, hipGetLastError());
-    if (int s = sec.wait("end")) return s;
-    if (to_host) { copy_guard.armed = false; PHZ_HIP(ctx, hipStreamSynchronize(ctx->copy_stream)); }          // the text is in the caller's region
-#undef RSV
-    h->chrom_blocks.assign((size_t)nchrom, 0); h->chrom_blk_vars.assign((size_t)nchrom, 0);
-    for (int c = 0; c < nchrom; c++) { h->chrom_blocks[(size_t)c] = h_cc[(size_t)nchrom + c]; h->chrom_blk_vars[(size_t)c] = h_cc[(size_t)2 * nchrom + c]; }
-    res->chrom_blocks = h->chrom_blocks.data(); res->chrom_blk_vars = h->chrom_blk_vars.data();
-    // the reference orders the chromosomes of the block files by the first BAM whose call file has a kept line on them (read_vars is keyed by the `chrom` that
-    // process_mapping_result returns, "" for a file without kept lines: phaser.py:1299, :573-574), VCF order inside a BAM.  A chromosome's covered variants are
-    // counted per (BAM of the first kept line, chromosome): its first BAM is the first of those counters that is not zero.
-    h->chrom_first_bam.assign((size_t)nchrom, -1);
-    for (int c = 0; c < nchrom; c++)
-        for (int b = 0; b < nb; b++)
-            if (h_cc[(size_t)3 * nchrom + (size_t)b * nchrom + c]) { h->chrom_first_bam[(size_t)c] = b; break; }
-    res->chrom_first_bam = h->chrom_first_bam.data();
-    res->n_blocks = nblocks; res->n_blk_vars = res->phased; res->n_components = ncomp; res->n_linked = n_linked;
-    res->allelic_rows = (int64_t)h_c64[4];
-    res->gpu_ms = sec.ms;
-    ctx->last_ms[PHZ_T_ROWS] = (float)sec.ms; ctx->total_ms[PHZ_T_ROWS] += sec.ms; ctx->launches[PHZ_T_ROWS]++;
+};
+
+}  // namespace
+
+// The pass is six sync-free sections, each ending in the host wait its line names (a grown read-set pool repeats the one of stats_read_sets_text_sizes)
+extern "C" int phz_rowsdev_run(phz_ctx *ctx, phz_rowsdev *h, const phz_rowsdev_opts *o, const double *slot_pv, const uint32_t *slot_txt_off,
+                               const char *slot_txt, phz_rowsdev_result *res) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || !h || !o || !slot_pv || !slot_txt_off || !slot_txt || !res) return PHZ_E_ARG;
+    Pass p(ctx, h, o, res);
+    if (int s = p.check_and_upload(slot_pv, slot_txt_off, slot_txt)) return s;
+    if (int s = p.sizes()) return s;                               // wait "sizes: members/comps/kept/keys"
+    if (int s = p.phase_and_blocks()) return s;                    // wait "phase + blocks: count" [, wait "blocks: count (after exceptions)"]
+    if (int s = p.stats_read_sets_text_sizes()) return s;          // wait "stats + read sets + text sizes"
+    if (int s = p.text_byte_offsets()) return s;                   // wait "text: byte offsets"
+    if (int s = p.write_text()) return s;                          // wait "end"
+    p.publish();
     return PHZ_OK;
 }
 
@@ -2830,8 +2810,7 @@ extern "C" int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, i
     DevBuf ns, l1, l2, cnt, pool;
     auto fin = [&](int code) { for (DevBuf *b : {&ns, &l1, &l2, &cnt, &pool}) if (b->p) (void)hipFree(b->p); return code; };
     int st = PHZ_OK;
-    if ((st = phz_reserve(ctx, ns, (size_t)nseg * 4)) || (st = phz_reserve(ctx, l1, (size_t)nseg * 4 + 4)) || (st = phz_reserve(ctx, l2, (size_t)nseg * 4 + 4)) ||
-        (st = phz_reserve(ctx, cnt, 256)) || (st = phz_reserve(ctx, pool, (size_t)4 << 20))) return fin(st);
+    if ((st = reserve_all(ctx, {{ns, (size_t)nseg * 4}, {l1, (size_t)nseg * 4 + 4}, {l2, (size_t)nseg * 4 + 4}, {cnt, 256}, {pool, (size_t)4 << 20}}))) return fin(st);
     for (int attempt = 0;; attempt++) {
         hipError_t e = hipMemsetAsync(cnt.p, 0, 256, sm);
         if (e != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_hap_counts", e));
@@ -2841,9 +2820,7 @@ extern "C" int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, i
         sg.big_list = P<uint32_t>(l1); sg.big_list2 = P<uint32_t>(l2); sg.huge_list = P<uint32_t>(l1);      // (a list is one piece: never huge)
         sg.counters = c; sg.huge_count = c + 4; sg.tickets = c + 5; sg.overflow = c + 20;
         sg.pool = P<uint32_t>(pool); sg.pool_cap = (uint32_t)std::min<size_t>(pool.cap / 4, 0xFFFFFFF0u);
-        hipLaunchKernelGGL(k_seg_small<2>, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, sm, sg);
-        hipLaunchKernelGGL((k_seg_big<2, 512, 64>), dim3((unsigned)std::min<int64_t>(nseg, 4096)), dim3(64), 0, sm, sg);
-        hipLaunchKernelGGL((k_seg_big<2, 4096, PHZ_SEG_THREADS>), dim3((unsigned)std::min<int64_t>(nseg, 768)), dim3(PHZ_SEG_THREADS), 0, sm, sg);
+        launch_read_sets<2>(sm, sg);
         uint32_t ovf = 0;
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&ovf, c + 20, 4, hipMemcpyDeviceToHost, sm);
@@ -2927,14 +2904,14 @@ extern "C" int phz_phase_components(phz_ctx *ctx, int64_t n_comp, const uint32_t
     if (st != PHZ_OK) return fin(st);
     Sections sec(ctx);
     sec.begin();
-    st = phase_enqueue(ctx, d[B_CS], d[B_MEM], d[B_ES], d[B_EK], P<int32_t>(d[B_EA]), P<int32_t>(d[B_EB]), P<int32_t>(d[B_CF]), n_comp, nmem, ne, max_block_size,
-                       d[B_AL], d[B_SUB], d[B_NSUB], d[B_CX], d[B_EX], d[B_EL], P<uint32_t>(d[B_CNT]));
+    const PhaseArgs pa{d[B_CS], d[B_MEM], d[B_ES], d[B_EK], P<int32_t>(d[B_EA]), P<int32_t>(d[B_EB]), P<int32_t>(d[B_CF]), ne, n_comp, nmem, ne, max_block_size,
+                       d[B_AL], d[B_SUB], d[B_NSUB], d[B_CX], d[B_EX], d[B_EL], P<uint32_t>(d[B_CNT])};          // (every pair is a kept pair here)
+    st = phase_enqueue(ctx, pa);
     if (st != PHZ_OK) return fin(st);
     uint32_t h_c32[4] = {0, 0, 0, 0};
     if (hipMemcpyAsync(h_c32, d[B_CNT].p, 12, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_phase_components"));
     st = sec.wait("phase components");
-    if (st == PHZ_OK) st = phase_exceptions(ctx, h_c32, d[B_CS], d[B_MEM], d[B_ES], d[B_EK], P<int32_t>(d[B_EA]), P<int32_t>(d[B_EB]), P<int32_t>(d[B_CF]), n_comp, nmem, ne, ne,
-                                            max_block_size, d[B_AL], d[B_SUB], d[B_NSUB], d[B_EX]);
+    if (st == PHZ_OK) st = phase_exceptions(ctx, h_c32, pa);
     if (st != PHZ_OK) return fin(st);
     hipError_t e = hipMemcpyAsync(sub_of, d[B_SUB].p, (size_t)nmem * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(alle_of, d[B_AL].p, (size_t)nmem, hipMemcpyDeviceToHost, ctx->stream);
