@@ -28,15 +28,18 @@ def oracle_lib(oracle_dir):
     return lib
 
 
-def oracle_map_readbatch(oracle_dir, rb, vpos, baseq, with_text=True):
-    """Run the C restatement on a synth.ReadBatch (CPU tensors). Returns (read_idx, var_idx, code, text list)."""
+def oracle_map_readbatch(oracle_dir, rb, vpos, baseq, with_text=True, ref_len=None):
+    """Run the C restatement on a synth.ReadBatch (CPU tensors). Returns (read_idx, var_idx, code, text list).
+    ref_len: per-variant REF length (default: ones, SNPs); a call's text then has up to 31 characters (32-byte slot, longer ones are cut)."""
     lib = oracle_lib(oracle_dir)
     n = len(rb)
     pos = np.ascontiguousarray(rb.pos.numpy().astype(np.int32))
     coff = np.ascontiguousarray(rb.cigar_off.numpy().astype(np.int64))
     cig = np.ascontiguousarray(rb.cigar.numpy().astype(np.uint32))
     seq = np.ascontiguousarray(rb.seq.numpy()); qual = np.ascontiguousarray(rb.qual.numpy())
-    vp = np.ascontiguousarray(np.asarray(vpos, dtype=np.int32)); rl = np.ones(len(vp), dtype=np.uint8)
+    vp = np.ascontiguousarray(np.asarray(vpos, dtype=np.int32))
+    rl = np.ones(len(vp), dtype=np.uint8) if ref_len is None else np.ascontiguousarray(np.asarray(ref_len, dtype=np.uint8))
+    assert len(rl) == len(vp)
     cap = n * 2 + 1024
     while True:
         o_r = np.zeros(cap, np.int32); o_v = np.zeros(cap, np.int32); o_c = np.zeros(cap, np.uint8)

@@ -427,6 +427,62 @@ def test_include_indels_pipeline(mapper):
     assert eng.vs.chroms["chr22"].is_general
 
 
+def indel_pipeline_inputs():
+    """Two chromosomes x two BAMs with shared QNAMEs; the reads carry the deletions, insertions and multi-base substitutions of the VCF on the
+    haplotype that has them (tests/indel_inputs.py)."""
+    import indel_inputs as ii
+    from phaser_amd import synth
+    contigs = [("chr4", 190214555), ("chr17", 83257441)]
+    vs = []; bams = {"y1.bam": {}, "y2.bam": {}}
+    for ci, (chrom, ln) in enumerate(contigs):
+        sh = ii.Shape("pipe", 9500 + ci, 0, 24_000, 90, start=300_000 + 1000 * ci, err=0.01, p_adj=0.03, intron=(50, 1500))
+        for bi, bam in enumerate(bams):
+            rb, vt = ii.make_pairs(sh, chrom, 2500, bi)
+            bams[bam][chrom] = "\n".join(synth.sam_lines(rb, contigs)) + "\n"
+        vs.append(vt.as_synth(seed=ci))
+    return "\n".join(synth.vcf_lines(vs)) + "\n", bams
+
+
+def indel_pipeline_oracle(oracle_build, tmp_path, vcf_text, bams):
+    import subprocess
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    import phasing_oracle as po
+    pool, _, _ = po.load_vcf(vcf_text)
+    ph = po.Phaser(po.bam_display_names(list(bams.keys())), max_block_size=8)
+    for bam, per_chrom in bams.items():
+        texts = []
+        for c in pool:
+            tp = tmp_path / "t.tsv"; tp.write_text("".join("\t".join(r) + "\n" for r in po.variant_table_rows(pool[c], include_indels=1)[0]))
+            op = tmp_path / "c.tsv"
+            subprocess.run([os.path.join(oracle_build, "rvm_oracle"), "--variant_table", str(tp), "--baseq", "10", "--o", str(op)],
+                           input=per_chrom[c].encode(), check=True)
+            texts.append(op.read_text())
+        ph.add_bam(texts)
+    want = ph.finish()
+    # the inputs reach what this test is about (oracle side): indels (REF and ALT of different lengths) inside phased blocks, seen on both alleles
+    is_indel = lambda uid: len(uid.split("_")[2]) != len(uid.split("_")[3])
+    in_blocks = set()
+    for row in want["haplotypic_counts"].split("\n")[1:]:
+        f = row.split("\t")
+        if len(f) > 4 and int(f[4]) >= 2:
+            in_blocks |= {u for u in f[3].split(",") if is_indel(u)}
+    both = [f for f in (row.split("\t") for row in want["allelic_counts"].split("\n")[1:]) if len(f) == 8 and is_indel(f[2]) and int(f[5]) > 0 and int(f[6]) > 0]
+    assert ph.phased > 50 and len(in_blocks) >= 20 and len(both) >= 20, (ph.phased, len(in_blocks), len(both))
+    return want, ph
+
+
+def test_fresh_seed_with_indels_vs_oracle(mapper, oracle_build, tmp_path):
+    """--include_indels 1 end to end on reads that show the indel alleles: K_map_general's codes 5 / 6 for multi-base alleles flow into K_tally and the
+    phasing; all five outputs vs the mapper oracle + phasing oracle."""
+    vcf_text, bams = indel_pipeline_inputs()
+    want, ph = indel_pipeline_oracle(oracle_build, tmp_path, vcf_text, bams)
+    got, eng = run_product(mapper, vcf_text, bams, "cuda", include_indels=1, max_block_size=8)
+    assert all(cv.is_general for cv in eng.vs.chroms.values())
+    for name in OUTPUTS:
+        assert canonical(name, got[name]) == canonical(name, want[name]), name
+    assert eng.phased == ph.phased
+
+
 def _opt_cases():
     return list(json.load(open(os.path.join(GOLD, "pipe_opts", "cases.json")))["cases"].keys())
 
