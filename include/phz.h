@@ -282,7 +282,9 @@ int phz_tally_fetch(phz_ctx *ctx, const phz_tally_out *out, int space);
 int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, int space);
 
 /* Connected components of the variant graph restricted to edges with keep != 0: label[v] = smallest variant
- * index of v's component.  edge_a == edge_b == NULL: the edge list of the last phz_tally (n_edges must match). */
+ * index of v's component.  edge_a == edge_b == NULL: the edge list of the last phz_tally (n_edges must match).
+ * Edge arrays handed over in PHZ_HOST space are checked before anything is launched: an endpoint outside [0, nv) is
+ * PHZ_E_ARG.  The resident list and arrays in PHZ_DEVICE space are NOT checked: their endpoints must lie in [0, nv). */
 int phz_components(phz_ctx *ctx, int64_t nv, int64_t n_edges, const int32_t *edge_a, const int32_t *edge_b,
                    const uint8_t *keep, int32_t *label, int space);
 

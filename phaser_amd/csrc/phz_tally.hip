@@ -1653,6 +1653,11 @@ extern "C" int phz_components(phz_ctx *ctx, int64_t nv, int64_t n_edges, const i
         if (n_edges != ctx->tally.n_edges || nv != ctx->tally.nv) return phz_fail(ctx, PHZ_E_ARG, "no resident edge list of that size");
         ea = ctx->tally.ea; eb = ctx->tally.eb;
     } else {
+        if (n_edges && (!edge_a || !edge_b)) return phz_fail(ctx, PHZ_E_ARG, "phz_components: one edge array is NULL");
+        if (space == PHZ_HOST)                  // a caller's host arrays: one bad endpoint would write outside parent[]
+            for (int64_t i = 0; i < n_edges; i++)
+                if (edge_a[i] < 0 || edge_a[i] >= nv || edge_b[i] < 0 || edge_b[i] >= nv)
+                    return phz_fail(ctx, PHZ_E_ARG, "phz_components: edge endpoint outside [0, nv)");
         if (int s = st.in(edge_a, (size_t)n_edges, space, &ea)) return s;
         if (int s = st.in(edge_b, (size_t)n_edges, space, &eb)) return s;
     }

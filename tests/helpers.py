@@ -223,15 +223,18 @@ def _noise(vc):
     return int(m[ok].sum()), int(mm[ok].sum())
 
 
-def component_labels_cpu(G, keep_all):
-    """label[v] = smallest variant of v's connected component over the kept edges (what phz_components returns)."""
+def component_labels_cpu(nv, ea, eb, keep=None):
+    """label[v] = smallest vertex of v's connected component over the edges (ea[i], eb[i]) with keep[i] != 0 (keep None: every edge): what
+    phz_components returns, by scipy."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
-    nv = G["nv"]
-    k = np.nonzero(keep_all)[0]
-    g = coo_matrix((np.ones(len(k), np.int8), (G["ea"][k], G["eb"][k])), shape=(nv, nv))
+    if nv == 0:
+        return np.zeros(0, np.int32)
+    ea = np.asarray(ea, dtype=np.int64); eb = np.asarray(eb, dtype=np.int64)
+    k = np.arange(len(ea)) if keep is None else np.nonzero(keep)[0]
+    g = coo_matrix((np.ones(len(k), np.int32), (ea[k], eb[k])), shape=(nv, nv))      # int32: a repeated edge sums its entries
     _, comp = connected_components(g, directed=False)
-    first = np.full(comp.max() + 1 if nv else 0, nv, dtype=np.int64)
+    first = np.full(comp.max() + 1, nv, dtype=np.int64)
     np.minimum.at(first, comp, np.arange(nv))
     return first[comp].astype(np.int32)
 
@@ -239,7 +242,7 @@ def component_labels_cpu(G, keep_all):
 def stub_gpu_stages(eng, saved):
     """Engine whose GPU stages (K_tally, components) answer from a fixture: the host stages run unchanged on CPU."""
     eng._tally_genome = lambda: genome_from_saved(saved, eng.chrom_list, len(eng.bam_names))
-    eng._component_labels = lambda keep_all: component_labels_cpu(eng.G, keep_all)
+    eng._component_labels = lambda keep_all: component_labels_cpu(eng.G["nv"], eng.G["ea"], eng.G["eb"], keep_all)
 
 
 # ------------------------------------------------------------------ kernel logic under the host-side HIP emulation (tests/hipemu)
@@ -300,4 +303,4 @@ def stub_emu_stages(eng, saved):
         G["resident"] = True; G["fetched"] = True; G["n_edges"] = len(G["ea"]); G["n_read_list"] = len(G["rl_qid"])
         return G
     eng._tally_genome = tally
-    eng._component_labels = lambda keep_all: component_labels_cpu(eng.G, keep_all)
+    eng._component_labels = lambda keep_all: component_labels_cpu(eng.G["nv"], eng.G["ea"], eng.G["eb"], keep_all)

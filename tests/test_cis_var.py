@@ -3,7 +3,9 @@
 CPU tests: the numpy replay of the Philox stream against rocRAND's own engine; K_boot under the host emulation (on-chip and
 forced-large paths) against the replay, bit for bit; the whole CLI with the replay in place of the launch against an independent
 pandas restatement of the reference's measure_effect + to_csv; the stream's replicate medians against numpy.random.choice's in
-distribution.  GPU tests: the product kernel against the replay, and a GTEx-shaped synthetic run for determinism."""
+distribution; the 16-bit packing at n = 32,768 and 65,535 and the refusal of 65,536.  GPU tests: the product kernel against the replay
+-- also in launches whose workgroups serve several groups in a row, at the 16-bit limits, on a reused context and in PHZ_DEVICE space --
+and a GTEx-shaped synthetic run for determinism."""
 import gzip
 import math
 import os
@@ -170,6 +172,75 @@ def test_kboot_emulated_matches_replay(lds_n):
                     lo = cis_var.lerp(got_os[g, k, 0], got_os[g, k, 1], bi.gamma_lo)
                     hi = cis_var.lerp(got_os[g, k, 2], got_os[g, k, 3], bi.gamma_hi)
                     assert _same(lo, np.percentile(want_reps[g, k], 2.5)) and _same(hi, np.percentile(want_reps[g, k], 97.5)), (bs, n, k)
+    finally:
+        L.phz_ctx_destroy(h)
+
+
+def _assert_boot_equals_replay(got, bi, what, reps=True):
+    """order statistics, sign counts and (reps) every replicate of every group of a launch against the numpy replay"""
+    got_os, got_sc, got_reps = got
+    want_os, want_sc, want_reps = replay_bootstrap(bi, want_replicates=reps)
+    sizes = np.diff(bi.off)
+    for g, n in enumerate(sizes.tolist()):
+        if n == 0:
+            assert np.isnan(got_os[g]).all() and (got_sc[g] == 0).all(), (what, g)
+            continue
+        if reps:
+            assert _same(got_reps[g], want_reps[g]), (what, g, n)
+        assert _same(got_os[g], want_os[g]), (what, g, n, got_os[g].tolist(), want_os[g].tolist())
+        assert np.array_equal(got_sc[g], want_sc[g]), (what, g, n, got_sc[g].tolist(), want_sc[g].tolist())
+
+
+# sizes 0 .. 129 of 40 groups at bs 41: with the lds_n = 8 build (grid 3) every workgroup serves 13 or 14 groups one after the other,
+# on-chip and global ones mixed
+MIXED_40 = [129, 0, 1, 64, 2, 8, 9, 127, 3, 65, 0, 7, 128, 1, 63, 5, 100, 4, 0, 33, 8, 9, 2, 129, 1, 17, 66, 0, 3, 126, 7, 8, 90, 1, 2, 64, 11, 0, 129, 6]
+PACKING_CASES = [(3, [65535]), (2, [65534, 3, 65535]), (41, MIXED_40), (2, [32768])]
+
+
+@pytest.mark.parametrize("lds_n", [None, 8])
+@pytest.mark.parametrize("case", range(len(PACKING_CASES)))
+def test_kboot_emulated_16bit_packing_and_workgroup_reuse(lds_n, case):
+    """The two 16-bit halves of a histogram word and of a rank at their limits -- bit 15 alone (n = 32,768), n = 65,535 -- and workgroups
+    that serve many groups in a row, against the replay bit for bit."""
+    from phaser_amd import _lib, cis_var
+    _lib.build()
+    L = _emu_lib(lds_n)
+    h = _emu_ctx(L)
+    bs, sizes = PACKING_CASES[case]
+    rng = np.random.default_rng(50 + case)
+    try:
+        vals, off = _groups(rng, sizes)
+        bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), bs)
+        _assert_boot_equals_replay(cis_var.bootstrap_gpu(L, h, bi, want_replicates=True), bi, (lds_n, bs))
+    finally:
+        L.phz_ctx_destroy(h)
+
+
+@pytest.mark.parametrize("lds_n", [None, 8])
+def test_kboot_group_of_65536_samples_is_refused(lds_n):
+    import ctypes as C
+    from phaser_amd import _lib, cis_var
+    _lib.build()
+    rng = np.random.default_rng(60)
+    with pytest.raises(cis_var.FatalError):
+        cis_var.BootInput(rng.normal(size=65536 + 3), np.array([0, 3, 65539], dtype=np.int64), np.zeros(2, np.uint64), 1, 3)
+    # the same group handed to the library in a phz_boot_in filled by hand: one more than the 16-bit halves can count
+    bi = cis_var.BootInput(rng.normal(size=65535), np.array([0, 65535], dtype=np.int64), np.zeros(1, np.uint64), 1, 3)
+    n = 65536
+    off = np.array([0, n], dtype=np.int64); sub = np.zeros(1, np.uint64)
+    rank = np.arange(n, dtype=np.uint32); rank |= rank << np.uint32(16)
+    v = np.sort(rng.normal(size=n)); va = np.sort(np.abs(v))
+    vp = lambda a: C.c_void_p(a.ctypes.data)
+    L = _emu_lib(lds_n)
+    h = _emu_ctx(L)
+    try:
+        s = bi.struct()
+        s.off = vp(off); s.subseq = vp(sub); s.rank = vp(rank); s.sorted_s = vp(v); s.sorted_a = vp(va); s.max_n = n
+        os_ = np.full((1, 2, 4), -5.0); sc = np.full((1, 2, 2), -5, dtype=np.int64)
+        assert L.phz_bootstrap_medians(h, C.byref(s), vp(os_), vp(sc), None, _lib.PHZ_HOST) == _lib.PHZ_E_ARG
+        assert np.all(os_ == -5.0) and np.all(sc == -5)
+        got = cis_var.bootstrap_gpu(L, h, bi)                    # the context is still usable, at the limit itself
+        assert not np.isnan(got[0]).any()
     finally:
         L.phz_ctx_destroy(h)
 
@@ -489,6 +560,146 @@ def test_kboot_gpu_matches_replay():
                 assert got_sc[g, k].tolist() == [(r > 0).sum(), (r < 0).sum()], (bs, n, k)
 
 
+# ---- workgroups that serve several groups of one launch (grid-stride over PHZ_BOOT_GRID = 1024 workgroups), the 16-bit limits, a reused context, PHZ_DEVICE
+BOOT_GRID = 1024            # PHZ_BOOT_GRID of the product build
+BOOT_LDS_N = 1024           # PHZ_BOOT_LDS_N: larger groups count in the global histogram
+REUSE_SIZES = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 1500]
+# what workgroup w meets in a row (groups w, w + 1024, w + 2048), planted on workgroups 0 .. 15 and again on 200 .. 215
+REUSE_PLANTED = [(64, 1025, 63), (1024, 1500, 1023), (1500, 1025, 1024), (1500, 1025, 1500), (0, 129, 0), (0, 1500, 3), (1500, 1, 1025), (1025, 1, 1),
+                 (1024, 1, 64), (1025, 0, 1500), (3, 1500, 2), (1500, 2, 1500), (1, 1025, 0), (128, 1500, 127), (1500, 1500, 1025), (65, 0, 1)]
+
+
+def _reuse_sizes(rng, n_groups=2500):
+    sizes = rng.choice(REUSE_SIZES, size=n_groups)
+    for base in (0, 200):
+        for i, seq in enumerate(REUSE_PLANTED):
+            sizes[[base + i, base + i + BOOT_GRID, base + i + 2 * BOOT_GRID]] = seq
+    # the sequences the launch must contain somewhere, checked on the sizes themselves
+    rows = [tuple(int(sizes[g]) for g in range(w, n_groups, BOOT_GRID)) for w in range(BOOT_GRID)]
+    assert min(len(r) for r in rows) == 2 and max(len(r) for r in rows) == 3
+    big = lambda n: n > BOOT_LDS_N
+    chip = lambda n: 0 < n <= BOOT_LDS_N
+    pairs = [(a, b) for r in rows for a, b in zip(r, r[1:])]
+    assert any(len(r) == 3 and chip(r[0]) and big(r[1]) and chip(r[2]) for r in rows)          # on-chip -> global -> on-chip
+    assert any(big(a) and big(b) and b < a for a, b in pairs)                                  # global -> global with a smaller n
+    assert any(a == 0 and chip(b) for a, b in pairs) and any(a == 0 and big(b) for a, b in pairs)      # non-empty right after empty
+    assert any(big(a) and b == 1 for a, b in pairs) and any(a == BOOT_LDS_N and b == 1 for a, b in pairs)      # large n, then n = 1
+    return sizes.tolist()
+
+
+def _reuse_subset(sizes):
+    """the groups compared at bs 10,000: every group of the planted workgroups 0 .. 15 (48 groups, every path change above)"""
+    return sorted(w + r * BOOT_GRID for w in range(len(REUSE_PLANTED)) for r in range(3))
+
+
+def _sub_input(bi, pick):
+    from phaser_amd import cis_var
+    return cis_var.BootInput(np.concatenate([bi.values[bi.off[g]:bi.off[g + 1]] for g in pick]),
+                             np.concatenate([[0], np.cumsum([bi.off[g + 1] - bi.off[g] for g in pick])]), bi.subseq[pick], bi.seed, bi.bs)
+
+
+@pytest.mark.gpu
+def test_kboot_gpu_reused_workgroups_match_replay_bs41():
+    """2,500 groups in one launch: every workgroup serves two or three groups and carries its LDS tables, its keys slice and its global
+    histogram slice from one to the next.  Every group of the launch against the replay."""
+    import time
+    from phaser_amd import _lib, cis_var
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(21)
+    sizes = _reuse_sizes(rng)
+    vals, off = _groups(rng, sizes)
+    bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), 41)
+    got = cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=True)
+    t0 = time.time()
+    _assert_boot_equals_replay(got, bi, "bs 41")
+    print("replay of %d groups (%d samples) at bs 41: %.1f s" % (len(sizes), int(off[-1]), time.time() - t0))
+
+
+@pytest.mark.gpu
+def test_kboot_gpu_reused_workgroups_match_replay_bs10000():
+    """The same launch shape at the product's bs: 48 groups (the three of each planted workgroup) against the replay."""
+    import time
+    from phaser_amd import _lib, cis_var
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(22)
+    sizes = _reuse_sizes(rng)
+    vals, off = _groups(rng, sizes)
+    bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), 10000)
+    got_os, got_sc, got_reps = cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=True)
+    pick = _reuse_subset(sizes)
+    sub = _sub_input(bi, pick)
+    t0 = time.time()
+    _assert_boot_equals_replay((got_os[pick], got_sc[pick], got_reps[pick]), sub, "bs 10000")
+    print("replay of %d groups (%d samples) at bs 10000: %.1f s" % (len(pick), int(sub.off[-1]), time.time() - t0))
+    empty = np.diff(off) == 0                                     # every other group: the cheap invariants
+    assert np.isnan(got_os[empty]).all() and not np.isnan(got_os[~empty]).any()
+    assert np.all(got_sc.sum(axis=2) <= 10000) and np.all(got_sc[empty] == 0)
+    assert np.all(got_os[~empty][:, :, 0] <= got_os[~empty][:, :, 3])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sizes", [[65535], [32768, 5, 65535, 32767]])
+def test_kboot_gpu_16bit_limits_match_replay(sizes):
+    from phaser_amd import _lib, cis_var
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(23 + len(sizes))
+    vals, off = _groups(rng, sizes)
+    bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), 3)
+    _assert_boot_equals_replay(cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=True), bi, sizes)
+
+
+@pytest.mark.gpu
+def test_kboot_gpu_one_context_through_changing_reservations():
+    """(max_n 5000, bs 500), (max_n 40, bs 41), (max_n 1500, bs 10001) on one context: the keys and histogram reservations and the
+    [grid][2][bs] layout change from call to call."""
+    from phaser_amd import _lib, cis_var
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(24)
+    for bs, sizes in ((500, [5000, 70, 1025, 3]), (41, [40, 1, 17, 0, 40]), (10001, [1500, 8, 1030])):
+        vals, off = _groups(rng, sizes)
+        bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), bs)
+        assert bi.max_n == sizes[0]
+        _assert_boot_equals_replay(cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=True), bi, (bs, sizes))
+
+
+def _bootstrap_device_space(ctx, bi, want_replicates):
+    """phz_bootstrap_medians with every input and output as a device tensor (PHZ_DEVICE)"""
+    import ctypes as C
+    import torch
+    from phaser_amd import _lib
+    dev = torch.device("cuda", ctx.device)
+    up = lambda a, dt: torch.from_numpy(a.view(dt)).to(dev)
+    t = {"off": up(bi.off, np.int64), "subseq": up(bi.subseq, np.int64), "rank": up(bi.rank, np.int32), "vs": up(bi.sorted_s, np.float64),
+         "va": up(bi.sorted_a, np.float64)}
+    G = bi.n_groups
+    os_ = torch.full((G, 2, 4), -5.0, dtype=torch.float64, device=dev); sc = torch.full((G, 2, 2), -5, dtype=torch.int64, device=dev)
+    reps = torch.full((G, 2, bi.bs), -5.0, dtype=torch.float64, device=dev) if want_replicates else None
+    s = bi.struct()
+    p = lambda x: C.c_void_p(x.data_ptr())
+    s.off = p(t["off"]); s.subseq = p(t["subseq"]); s.rank = p(t["rank"]); s.sorted_s = p(t["vs"]); s.sorted_a = p(t["va"])
+    torch.cuda.synchronize(dev)
+    ctx.check(ctx.lib.phz_bootstrap_medians(ctx.h, C.byref(s), p(os_), p(sc), p(reps) if want_replicates else None, _lib.PHZ_DEVICE))
+    return os_.cpu().numpy(), sc.cpu().numpy(), (reps.cpu().numpy() if want_replicates else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("want_replicates", [True, False])
+def test_kboot_gpu_device_space_equals_host_space_and_replay(want_replicates):
+    from phaser_amd import _lib, cis_var
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(25)
+    sizes = [7, 0, 1024, 1025, 1, 300, 2000, 64, 0, 1500, 2]
+    vals, off = _groups(rng, sizes)
+    bi = cis_var.BootInput(vals, off, rng.integers(0, 2 ** 40, len(sizes), dtype=np.uint64), int(rng.integers(0, 2 ** 63)), 200)
+    host = cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=want_replicates)
+    dev = _bootstrap_device_space(ctx, bi, want_replicates)
+    assert _same(dev[0], host[0]) and np.array_equal(dev[1], host[1])
+    if want_replicates:
+        live = np.diff(off) > 0                                   # the replicates of an empty group are not written
+        assert _same(dev[2][live], host[2][live])
+    _assert_boot_equals_replay(dev, bi, "PHZ_DEVICE", reps=want_replicates)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("matrix,tbi", [("bgzf", True), ("plain", False)])
 def test_cis_var_gpu_matches_restatement(tmp_path, matrix, tbi):
@@ -502,7 +713,8 @@ def test_cis_var_gpu_matches_restatement(tmp_path, matrix, tbi):
 
 @pytest.mark.gpu
 def test_cis_var_gpu_gtex_shaped_is_deterministic(tmp_path):
-    """2,000 pairs x 670 samples at bs 10,000: 64 random groups equal the replay; two CLI runs and --t 1 / --t 16 give the same bytes."""
+    """2,000 pairs x 670 samples at bs 10,000: 64 random groups equal the replay, launched on their own and as part of the launch of all
+    4,000 groups; two CLI runs and --t 1 / --t 16 give the same bytes."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import cis_var_scale
     from phaser_amd import _lib, cis_var
@@ -531,6 +743,10 @@ def test_cis_var_gpu_gtex_shaped_is_deterministic(tmp_path):
     got_os, got_sc, _ = cis_var.bootstrap_gpu(ctx.lib, ctx.h, sub)
     want_os, want_sc, _ = replay_bootstrap(sub)
     assert _same(got_os, want_os) and np.array_equal(got_sc, want_sc)
+    # ... and the same 64 groups taken from the launch of the whole run, the one in which a workgroup serves several groups in a row
+    assert bi.n_groups > 2 * BOOT_GRID
+    full_os, full_sc, _ = cis_var.bootstrap_gpu(ctx.lib, ctx.h, bi, want_replicates=False)
+    assert _same(full_os[pick], want_os) and np.array_equal(full_sc[pick], want_sc)
 
 
 # ------------------------------------------------------------------------------------------------ VCF lookup: index path = whole-file scan = an independent reader
