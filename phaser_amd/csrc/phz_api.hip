@@ -57,7 +57,7 @@ int phz_ctx_destroy(phz_ctx *c) {
     for (DevBuf &b : c->tally_buf) free_buf(b);
     for (DevBuf &b : c->import_buf) free_buf(b);
     for (DevBuf &b : c->resident_vars) free_buf(b);
-    free_buf(c->tally_qcount); free_buf(c->scan_state);
+    free_buf(c->tally_qcount); free_buf(c->tally_table); free_buf(c->scan_state);
     free_buf(c->boot_keys); free_buf(c->boot_hist);
     if (c->h_scalars.p) (void)hipHostFree(c->h_scalars.p);
     if (c->mail_host.p) (void)hipHostFree(c->mail_host.p);
@@ -170,6 +170,7 @@ __global__ __launch_bounds__(64) void k_mail(MailArgs a, char *dst) {
 }
 }  // namespace
 int PhzMail::send() {
+    if (overflow) return phz_fail(ctx, PHZ_E_ARG, "PhzMail: more values queued than it holds");
     if (!n) return PHZ_OK;
     if (int s = phz_reserve(ctx, ctx->mail_dev, total + 64)) return s;
     if (int s = phz_reserve_host(ctx, ctx->mail_host, total + 64)) return s;

@@ -555,7 +555,7 @@ int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names
     hipStream_t cs[NCOPY_MAX];
     for (int t = 0; t < NCOPY_MAX; t++) cs[t] = nullptr;
     for (int t = 0; t < NCOPY; t++) if (hipStreamCreateWithFlags(&cs[t], hipStreamNonBlocking) != hipSuccess) cs[t] = nullptr;
-    if (phz_reserve(ctx, ctx->scalars, 64) != PHZ_OK || phz_reserve(ctx, ctx->scratch[11], mem.size() * (size_t)phz_inflate_scratch_bytes_per_member()) != PHZ_OK) {
+    if (phz_reserve(ctx, ctx->scalars, 64) != PHZ_OK || phz_reserve(ctx, ctx->scratch[SC_INFLATE_LENS], mem.size() * (size_t)phz_inflate_scratch_bytes_per_member()) != PHZ_OK) {
         bam_give_back(&ctx->bam_comp, d_comp, d_comp_cap); (void)hipFree(d_mem); for (auto c : cs) if (c) (void)hipStreamDestroy(c);
         (void)hipGetLastError();
         delete h; phz_bam_plan_release(&plan); return PHZ_E_NOMEM;
@@ -697,7 +697,7 @@ int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names
             // the K_inflate launches take turns on n_is streams: a chunk's members start while the previous launches are still running (see above)
             hipStream_t si = n_is > 1 ? is[(size_t)(n_launch % n_is)] : sm;
             st = phz_inflate_launch(ctx, (const uint8_t *)d_comp, (const phz_bgzf_member *)d_mem, (int64_t)i0, (int64_t)(i1 - i0), (uint8_t *)h->d_stream,
-                                    (uint8_t *)ctx->scratch[11].p, d_status, si);
+                                    (uint8_t *)ctx->scratch[SC_INFLATE_LENS].p, d_status, si);
             if (st == PHZ_OK && crc_on) st = phz_crc_launch(ctx, (const phz_bgzf_member *)d_mem, (int64_t)i0, (int64_t)(i1 - i0), (const uint8_t *)h->d_stream, d_crc, d_status, si);
             n_launch++;
             i0 = i1;
@@ -785,7 +785,7 @@ int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names
         if (hipStreamSynchronize(sm) != hipSuccess) return fail(PHZ_E_HIP, "boundary repair");
     }
     hipLaunchKernelGGL(k_seg_kept, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, sm, (const SegOut *)dso, nseg, dkept);
-    if (int s2 = scan_excl(ctx, dkept, dkbase, nseg, ctx->scratch[6])) return fail(s2, nullptr);
+    if (int s2 = scan_excl(ctx, dkept, dkbase, nseg, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
     if (hipMemcpyAsync(&total_kept, dkbase + nseg, 4, hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
         return fail(PHZ_E_HIP, "segment read-back");
     {   // records sorted (inside segments and across them); 64-bit totals within the 32-bit scans
@@ -821,9 +821,9 @@ int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names
     h->d_ref_begin = (int64_t *)w;
     if (nk > 0) {
         hipLaunchKernelGGL(k_hop<1>, dim3(gseg), dim3(64), 0, sm, d, (const Seg *)dsegs, nseg, (const uint64_t *)dstart, F, dso, (const uint32_t *)dkbase, h->K);
-        if (int s2 = scan_excl(ctx, h->K.nops, h->co, nk, ctx->scratch[6])) return fail(s2, nullptr);
-        if (int s2 = scan_excl(ctx, h->K.sq, h->so, nk, ctx->scratch[6])) return fail(s2, nullptr);
-        if (int s2 = scan_excl(ctx, h->K.lqn, h->qo, nk, ctx->scratch[6])) return fail(s2, nullptr);
+        if (int s2 = scan_excl(ctx, h->K.nops, h->co, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+        if (int s2 = scan_excl(ctx, h->K.sq, h->so, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+        if (int s2 = scan_excl(ctx, h->K.lqn, h->qo, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
     } else {
         (void)hipMemsetAsync(h->co, 0, 4, sm); (void)hipMemsetAsync(h->so, 0, 4, sm); (void)hipMemsetAsync(h->qo, 0, 4, sm);
     }
@@ -909,17 +909,17 @@ int phz_intern_device(phz_ctx *ctx, const char *qnames, const uint32_t *qname_of
     uint64_t cap = 1024;
     while (cap < 2 * (uint64_t)(n + n_old)) cap <<= 1;
     DevBuf *S = ctx->scratch;
-    if (int s = phz_reserve(ctx, S[7], cap * 4)) return s;
-    if (int s = phz_reserve(ctx, S[8], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[9], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[10], ((size_t)n + 1) * 4)) return s;
-    uint32_t *table = (uint32_t *)S[7].p, *slot_of = (uint32_t *)S[8].p, *first = (uint32_t *)S[9].p, *rank = (uint32_t *)S[10].p;
+    if (int s = phz_reserve(ctx, S[SC_INTERN_TABLE], cap * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_INTERN_SLOT_OF], (size_t)n * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_INTERN_FIRST], (size_t)n * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_INTERN_RANK], ((size_t)n + 1) * 4)) return s;
+    uint32_t *table = (uint32_t *)S[SC_INTERN_TABLE].p, *slot_of = (uint32_t *)S[SC_INTERN_SLOT_OF].p, *first = (uint32_t *)S[SC_INTERN_FIRST].p, *rank = (uint32_t *)S[SC_INTERN_RANK].p;
     PHZ_HIP(ctx, hipMemsetAsync(table, 0xff, cap * 4, sm));
     const unsigned grid = (unsigned)((n + 255) / 256);
     if (n_old > 0) hipLaunchKernelGGL(k_intern_old, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, sm, store, store_off, n_old, table, (uint32_t)(cap - 1));
     hipLaunchKernelGGL(k_intern_insert, dim3(grid), dim3(256), 0, sm, qnames, qname_off, n, store, store_off, table, (uint32_t)(cap - 1), slot_of);
     hipLaunchKernelGGL(k_intern_first, dim3(grid), dim3(256), 0, sm, (const uint32_t *)table, (const uint32_t *)slot_of, n, first);
-    if (int s = scan_excl(ctx, first, rank, n, S[6])) return s;
+    if (int s = scan_excl(ctx, first, rank, n, S[SC_BAM_SCAN_TMP])) return s;
     hipLaunchKernelGGL(k_intern_assign, dim3(grid), dim3(256), 0, sm, (const uint32_t *)table, (const uint32_t *)slot_of, (const uint32_t *)first,
                        (const uint32_t *)rank, n, (int32_t)n_old, qid, first_idx);
     PHZ_HIP(ctx, hipGetLastError());
@@ -942,11 +942,11 @@ int phz_names_append_device(phz_ctx *ctx, const char *qnames, const uint32_t *qn
     const unsigned grid = (unsigned)((m + 255) / 256);
     if (!dst) {
         DevBuf *S = ctx->scratch;
-        if (int s = phz_reserve(ctx, S[8], (size_t)m * 4)) return s;
-        if (int s = phz_reserve(ctx, S[9], ((size_t)m + 1) * 4)) return s;
-        uint32_t *len = (uint32_t *)S[8].p, *pre = (uint32_t *)S[9].p;
+        if (int s = phz_reserve(ctx, S[SC_NAMES_LEN], (size_t)m * 4)) return s;
+        if (int s = phz_reserve(ctx, S[SC_NAMES_PRE], ((size_t)m + 1) * 4)) return s;
+        uint32_t *len = (uint32_t *)S[SC_NAMES_LEN].p, *pre = (uint32_t *)S[SC_NAMES_PRE].p;
         hipLaunchKernelGGL(k_names_len, dim3(grid), dim3(256), 0, sm, qname_off, first_idx, m, len);
-        if (int s = scan_excl(ctx, len, pre, m, S[6])) return s;
+        if (int s = scan_excl(ctx, len, pre, m, S[SC_BAM_SCAN_TMP])) return s;
         uint32_t total = 0;
         PHZ_HIP(ctx, hipMemcpyAsync(&total, pre + m, 4, hipMemcpyDeviceToHost, sm));
         PHZ_HIP(ctx, hipStreamSynchronize(sm));

@@ -404,11 +404,11 @@ extern "C" int phz_bgzf_inflate_device(phz_ctx *ctx, const uint8_t *comp, const 
     if (n_members == 0) return PHZ_OK;
     hipStream_t sm = ctx->stream;
     if (int s = phz_reserve(ctx, ctx->scalars, 64)) return s;
-    if (int s = phz_reserve(ctx, ctx->scratch[11], (size_t)n_members * SCRATCH)) return s;
+    if (int s = phz_reserve(ctx, ctx->scratch[SC_INFLATE_LENS], (size_t)n_members * SCRATCH)) return s;
     int *d_status = (int *)ctx->scalars.p;
     PHZ_HIP(ctx, hipMemsetAsync(d_status, 0, 4, sm));
     PHZ_HIP(ctx, hipEventRecord(ctx->ev0, sm));
-    hipLaunchKernelGGL(k_inflate, dim3((unsigned)((n_members + IL - 1) / IL)), dim3(IL), 0, sm, comp, (const Member *)members, n_members, out, (uint8_t *)ctx->scratch[11].p, d_status);
+    hipLaunchKernelGGL(k_inflate, dim3((unsigned)((n_members + IL - 1) / IL)), dim3(IL), 0, sm, comp, (const Member *)members, n_members, out, (uint8_t *)ctx->scratch[SC_INFLATE_LENS].p, d_status);
     PHZ_HIP(ctx, hipGetLastError());
     PHZ_HIP(ctx, hipEventRecord(ctx->ev1, sm));
     PHZ_HIP(ctx, hipMemcpyAsync(bad, d_status, 4, hipMemcpyDeviceToHost, sm));

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -12,6 +13,29 @@
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+};
+
+// Names of the per-call scratch slots ctx->scratch[...], grouped by the entry points that use them.  THE RULE: a slot holds nothing that must survive the
+// return of the entry point that wrote it -- every entry point reserves and fills what it reads, which is why owners may (and do) share a number.  Whatever
+// has to outlive a call has a ctx member of its own (tally_qcount, tally_table, tally_buf, ...).
+enum PhzScratch {
+    // AS histograms (phz_as_histogram / _batch / _sparse, phz_as_cutoff_enqueue): histogram + flags + occupied bins
+    SC_AS_HIST = 0,
+    // phz_tally (slots 1 and 7 are not used by it: 7 held the variant-pair table, now ctx->tally_table)
+    SC_T_TOUCHED = 2, SC_T_CNT_T = 3, SC_T_BASE_T = 4, SC_T_ITEMS = 5, SC_T_COUNTERS = 6, SC_T_USEDKEY = 8, SC_T_DEG = 9, SC_T_EOFF = 10, SC_T_EB = 11, SC_T_ESLOT = 12,
+    SC_T_SCAN_TMP = 13, SC_T_USED = 14, SC_T_MISC = 15, SC_T_EA = 19, SC_T_PROFILE = 20,
+    // phz_components
+    SC_UF_PARENT = 16,
+    // K_map (phz_map_reads / _batch): per-tile totals, packed staging slots, first overflow slot per tile, PHZ_MAP_DBG cycle counts
+    SC_MAP_TILE_TOTAL = 17, SC_MAP_STAGE = 18, SC_MAP_TILE_OVF = 19, SC_MAP_PROFILE = 21,
+    // K_map_general (phz_map_reads_general)
+    SC_GEN_N_CALLS = 0, SC_GEN_TILE_SUMS = 1, SC_GEN_CALL_BASE = 2, SC_GEN_TEXT_BASE = 3, SC_GEN_WINDOW = 4, SC_GEN_DESC = 5, SC_GEN_SCAN_TMP = 6, SC_GEN_WORKLIST = 7,
+    SC_GEN_WORKLIST_N = 8, SC_GEN_SIDE = 9,
+    // device BAM path (phz_bamdev.hip): scan temporary of the decode, QNAME interning (hash table, slot / first flag / rank per record), name lengths + offsets
+    SC_BAM_SCAN_TMP = 6, SC_INTERN_TABLE = 7, SC_INTERN_SLOT_OF = 8, SC_INTERN_FIRST = 9, SC_INTERN_RANK = 10, SC_NAMES_LEN = 8, SC_NAMES_PRE = 9,
+    // K_inflate: code lengths + cold table part per member
+    SC_INFLATE_LENS = 11,
+    SC_COUNT = 24
 };
 
 struct phz_ctx {
@@ -44,8 +68,8 @@ struct phz_ctx {
     // staging for PHZ_HOST callers
     DevBuf r_pos, r_coff, r_cig, r_soff, r_seq, r_qual, v_pos, v_reflen;
     DevBuf c_read, c_var, c_code, c_aux0, c_aux1;
-    // generic per-call scratch slots (tally / components), grown on demand and reused across calls
-    DevBuf scratch[24];
+    // generic per-call scratch slots (PhzScratch), grown on demand and reused across calls
+    DevBuf scratch[SC_COUNT];
     // device copies of PHZ_HOST callers' arrays (Staging): slot k of a call reuses stage_pool[k], grown on demand, so the
     // steady state allocates nothing
     std::vector<DevBuf> stage_pool;
@@ -59,6 +83,7 @@ struct phz_ctx {
     uint64_t tally_table_cap = 0;      // slots of the variant-pair table that the last phz_tally needed
     DevBuf boot_keys, boot_hist;       // K_boot: replicate medians per resident block, histograms of groups too large for LDS
     DevBuf tally_qcount;               // lines per QNAME: all zero between phz_tally calls (never shared with other stages)
+    DevBuf tally_table;                // variant-pair hash table of phz_tally: all zero between calls (k_edge_out leaves it so), never shared with other stages
     // results of the last phz_tally, resident in HBM until the next one (phz_tally_fetch / phz_components read them)
     struct {
         int64_t nv = 0, n_lines = 0, n_kept = 0, n_edges = 0, n_rl = 0;
@@ -83,10 +108,10 @@ struct PhzMail {
     static constexpr int MAX = 16;
     phz_ctx *ctx;
     const void *src[MAX]; uint32_t bytes[MAX], off[MAX];
-    int n = 0; uint32_t total = 0;
+    int n = 0; uint32_t total = 0; bool overflow = false;
     explicit PhzMail(phz_ctx *c) : ctx(c) {}
     int add(const void *dev, size_t nbytes) {          // -> slot; the value is at<T>(slot) after send() + a host wait on the ctx stream
-        if (n >= MAX) return -1;
+        if (n >= MAX) { overflow = true; return -1; }          // (send() then fails: nobody reads at<T>(-1))
         src[n] = dev; bytes[n] = (uint32_t)nbytes; off[n] = total;
         total += ((uint32_t)nbytes + 7u) & ~7u;
         return n++;
@@ -103,6 +128,13 @@ struct PhzEnter {
 int phz_fail(phz_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess);
 int phz_reserve(phz_ctx *ctx, DevBuf &b, size_t bytes);
 int phz_reserve_host(phz_ctx *ctx, DevBuf &b, size_t bytes);      // pinned host memory
+// reserve a list of (buffer, bytes); the first failure ends it
+struct Rsv { DevBuf &b; size_t bytes; };
+inline int reserve_all(phz_ctx *ctx, std::initializer_list<Rsv> list) {
+    for (const Rsv &r : list) if (int s = phz_reserve(ctx, r.b, r.bytes)) return s;
+    return PHZ_OK;
+}
+inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }          // workgroups of 256 threads over n items
 
 #define PHZ_HIP(ctx, call)                                                      \
     do {                                                                        \

@@ -1124,9 +1124,9 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
         ctx->map_ev.resize(2, nullptr);
         for (auto &e : ctx->map_ev) if (!e) PHZ_HIP(ctx, hipEventCreate(&e));
     }
-    DevBuf *S = ctx->scratch;      // 17: tile_total, 18: packed staging slots
+    DevBuf *S = ctx->scratch;
     if (int s = phz_reserve(ctx, ctx->tile_w0, (size_t)ntiles * 16)) return s;
-    if (int s = phz_reserve(ctx, S[17], (size_t)ntiles * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_MAP_TILE_TOTAL], (size_t)ntiles * 4)) return s;
     const int nchunks = (int)((ntiles + 1023) / 1024);
     if (int s = phz_reserve(ctx, ctx->desc, (size_t)ntiles * 4 + (size_t)nchunks * 24 + 64)) return s;
     int32_t *tile_pref = (int32_t *)ctx->desc.p;
@@ -1135,7 +1135,7 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
     int32_t *chunk_max = (int32_t *)(chunk_base + nchunks);
     if (int s = phz_reserve(ctx, ctx->scalars, (size_t)8 * (m + 3) + 128)) return s;           // [0] total, [1] densest tile, [2, 2 + m) calls per shard, [2 + m] overflow-area cursor, then the OvfArea record
     if (int s = phz_reserve_host(ctx, ctx->h_scalars, (size_t)8 * (m + 3) + 128)) return s;
-    if (int s = phz_reserve(ctx, S[19], (size_t)ntiles * 4)) return s;                          // tile_ovf
+    if (int s = phz_reserve(ctx, S[SC_MAP_TILE_OVF], (size_t)ntiles * 4)) return s;                          // tile_ovf
     unsigned long long *scal = (unsigned long long *)ctx->h_scalars.p;
     // Staging: every tile owns a slot of slot_cap calls (half a tile's records: the typical RNA-seq tile has ~60) and a tile with more takes a stretch of
     // the OVERFLOW AREA behind the slots (one cursor step per such tile).  The area starts at a quarter of the slots' size and is kept at what the densest
@@ -1153,15 +1153,15 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
         if (ctx->map_ovf_cap < 65536) ctx->map_ovf_cap = 65536;
         const size_t slots = base_slots + (size_t)ctx->map_ovf_cap;
         if (slots >= 0xFFFFFFF0ull) return phz_fail(ctx, PHZ_E_ARG, "K_map staging area beyond 2^32 slots: submit the shards in smaller batches");
-        if (int s = phz_reserve(ctx, S[18], slots * 16)) return s;
+        if (int s = phz_reserve(ctx, S[SC_MAP_STAGE], slots * 16)) return s;
         MapBatch bt;
         bt.shards = d_shards; bt.tile0 = d_tile0; bt.n_shards = m; bt.baseq = baseq;
-        bt.stage = (uint2 *)S[18].p; bt.side = (uint32_t *)((char *)S[18].p + slots * 8); bt.slots = (int64_t)slots;
-        bt.tile_w0 = (int32_t *)ctx->tile_w0.p; bt.tile_total = (int32_t *)S[17].p;
+        bt.stage = (uint2 *)S[SC_MAP_STAGE].p; bt.side = (uint32_t *)((char *)S[SC_MAP_STAGE].p + slots * 8); bt.slots = (int64_t)slots;
+        bt.tile_w0 = (int32_t *)ctx->tile_w0.p; bt.tile_total = (int32_t *)S[SC_MAP_TILE_TOTAL].p;
         bt.slot_cap = slot_cap; bt.ntiles = ntiles;
         {
             OvfArea *h_ov = (OvfArea *)((char *)ctx->h_scalars.p + (size_t)8 * (m + 3) + 64);          // (pinned; behind the words the read-back fills)
-            h_ov->tile_first = (uint32_t *)S[19].p; h_ov->cursor = (unsigned long long *)ctx->scalars.p + (2 + m); h_ov->base = (long long)base_slots; h_ov->cap = (long long)ctx->map_ovf_cap;
+            h_ov->tile_first = (uint32_t *)S[SC_MAP_TILE_OVF].p; h_ov->cursor = (unsigned long long *)ctx->scalars.p + (2 + m); h_ov->base = (long long)base_slots; h_ov->cap = (long long)ctx->map_ovf_cap;
             OvfArea *d_ov = (OvfArea *)((char *)ctx->map_tab.p + tab_bytes + (size_t)m * 8);            // in K_map's own buffer: ctx->scalars is shared scratch
             // (uploaded only when it changed -- like the shard table --; the cursor is zeroed by the pre-pass kernel: no extra operation on the stream per step)
             long long img[5] = {(long long)(intptr_t)h_ov->tile_first, (long long)(intptr_t)h_ov->cursor, h_ov->base, h_ov->cap, (long long)(intptr_t)d_ov};
@@ -1173,7 +1173,7 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
         }
         { const char *e = getenv("PHZ_MAP_DBG"); bt.dbg = e ? atoi(e) : 0; }
         bt.prof = nullptr;
-        if (bt.dbg & 2048) { if (int s = phz_reserve(ctx, S[21], (size_t)ntiles * 64)) return s; bt.prof = (unsigned long long *)S[21].p; }
+        if (bt.dbg & 2048) { if (int s = phz_reserve(ctx, S[SC_MAP_PROFILE], (size_t)ntiles * 64)) return s; bt.prof = (unsigned long long *)S[SC_MAP_PROFILE].p; }
         hipLaunchKernelGGL(k_tile_window, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, sm, bt, tile_reads);
         PHZ_HIP(ctx, hipEventRecord(ctx->map_ev[0], sm));
         unsigned dyn_lds = 0;          // experiment: dynamic LDS nobody uses, to bound the workgroups per CU (PHZ_MAP_DYNLDS bytes)
@@ -1185,7 +1185,7 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
         else PHZ_LAUNCH_MAP(256, 2);
 #undef PHZ_LAUNCH_MAP
         PHZ_HIP(ctx, hipEventRecord(ctx->map_ev[1], sm));
-        hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)nchunks), dim3(1024), 0, sm, (const int32_t *)S[17].p, ntiles, tile_pref, chunk_sum,
+        hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)nchunks), dim3(1024), 0, sm, (const int32_t *)S[SC_MAP_TILE_TOTAL].p, ntiles, tile_pref, chunk_sum,
                            chunk_max);
         hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(1024), 0, sm, (const int64_t *)chunk_sum, (const int32_t *)chunk_max, nchunks, chunk_base,
                            (unsigned long long *)ctx->scalars.p);
@@ -1194,9 +1194,9 @@ static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_v
         CompactArgs c;
         c.stage = bt.stage; c.side = bt.side; c.slots = bt.slots;
         c.shards = d_shards; c.tile0 = d_tile0; c.n_shards = m;
-        c.tile_total = (const int32_t *)S[17].p; c.tile_pref = tile_pref; c.chunk_base = chunk_base; c.shard_base = d_shard_base;
+        c.tile_total = (const int32_t *)S[SC_MAP_TILE_TOTAL].p; c.tile_pref = tile_pref; c.chunk_base = chunk_base; c.shard_base = d_shard_base;
         c.tile_w0 = bt.tile_w0;
-        c.slot_cap = slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = (const uint32_t *)S[19].p;
+        c.slot_cap = slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = (const uint32_t *)S[SC_MAP_TILE_OVF].p;
         hipLaunchKernelGGL(k_compact, dim3((unsigned)((ntiles + 4 * CT - 1) / (4 * CT))), dim3(256), 0, sm, c);
         PHZ_HIP(ctx, hipGetLastError());
         PHZ_HIP(ctx, hipMemcpyAsync(scal, ctx->scalars.p, (size_t)8 * (m + 3), hipMemcpyDeviceToHost, sm));

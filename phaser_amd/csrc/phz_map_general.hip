@@ -559,34 +559,34 @@ extern "C" int phz_map_reads_general(phz_ctx *ctx, const phz_reads *reads, const
     if (int s = st.in(vars->allele_bytes, (size_t)vars->n_allele_bytes, space, &a.abytes)) return s;
     a.n = n; a.nv = (int)nv; a.baseq = baseq;
     DevBuf *S = ctx->scratch;
-    if (int s = phz_reserve(ctx, S[0], (size_t)n * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_N_CALLS], (size_t)n * 4)) return s;
     const unsigned grid = (unsigned)((n + GEN_TILE - 1) / GEN_TILE);
-    if (int s = phz_reserve(ctx, S[1], (size_t)(grid + 1) * 16)) return s;
-    if (int s = phz_reserve(ctx, S[2], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[3], (size_t)n * 4)) return s;
-    a.n_calls = (uint32_t *)S[0].p;
-    a.tile_calls = (uint32_t *)S[1].p; a.tile_text = a.tile_calls + grid;
+    if (int s = phz_reserve(ctx, S[SC_GEN_TILE_SUMS], (size_t)(grid + 1) * 16)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_CALL_BASE], (size_t)n * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_TEXT_BASE], (size_t)n * 4)) return s;
+    a.n_calls = (uint32_t *)S[SC_GEN_N_CALLS].p;
+    a.tile_calls = (uint32_t *)S[SC_GEN_TILE_SUMS].p; a.tile_text = a.tile_calls + grid;
     uint32_t *cb = a.tile_text + grid, *tb = cb + grid + 1;
     a.tile_cbase = cb; a.tile_tbase = tb;
-    a.call_base = (uint32_t *)S[2].p; a.text_base = (uint32_t *)S[3].p;
+    a.call_base = (uint32_t *)S[SC_GEN_CALL_BASE].p; a.text_base = (uint32_t *)S[SC_GEN_TEXT_BASE].p;
     hipStream_t sm = ctx->stream;
-    if (int s = phz_reserve(ctx, S[4], (size_t)grid * 8)) return s;
-    if (int s = phz_reserve(ctx, S[5], (size_t)nv * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_WINDOW], (size_t)grid * 8)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_DESC], (size_t)nv * 4)) return s;
     if (n >= (1ll << 32)) return phz_fail(ctx, PHZ_E_ARG, "too many records in one shard");
-    if (int s = phz_reserve(ctx, S[7], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[8], 64)) return s;
-    if (int s = phz_reserve(ctx, S[9], (size_t)n * 16)) return s;
-    a.side = (uint4 *)S[9].p;
-    a.win = (const int32_t *)S[4].p; a.desc = (const uint32_t *)S[5].p;
-    a.wl = (uint32_t *)S[7].p; a.wl_n = (uint32_t *)S[8].p;
+    if (int s = phz_reserve(ctx, S[SC_GEN_WORKLIST], (size_t)n * 4)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_WORKLIST_N], 64)) return s;
+    if (int s = phz_reserve(ctx, S[SC_GEN_SIDE], (size_t)n * 16)) return s;
+    a.side = (uint4 *)S[SC_GEN_SIDE].p;
+    a.win = (const int32_t *)S[SC_GEN_WINDOW].p; a.desc = (const uint32_t *)S[SC_GEN_DESC].p;
+    a.wl = (uint32_t *)S[SC_GEN_WORKLIST].p; a.wl_n = (uint32_t *)S[SC_GEN_WORKLIST_N].p;
     PHZ_HIP(ctx, hipMemsetAsync(a.wl_n, 0, 4, sm));
     PHZ_HIP(ctx, hipEventRecord(ctx->ev0, sm));
-    hipLaunchKernelGGL(k_gen_window, dim3((grid + 255) / 256), dim3(256), 0, sm, a.pos, n, GEN_TILE, a.vpos, (int)nv, (int64_t)grid, (int32_t *)S[4].p);
-    hipLaunchKernelGGL(k_gen_desc, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, sm, a.ref_len, a.aoff, a.abytes, (int)nv, (uint32_t *)S[5].p);
+    hipLaunchKernelGGL(k_gen_window, dim3((grid + 255) / 256), dim3(256), 0, sm, a.pos, n, GEN_TILE, a.vpos, (int)nv, (int64_t)grid, (int32_t *)S[SC_GEN_WINDOW].p);
+    hipLaunchKernelGGL(k_gen_desc, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, sm, a.ref_len, a.aoff, a.abytes, (int)nv, (uint32_t *)S[SC_GEN_DESC].p);
     hipLaunchKernelGGL(k_map_general, dim3(grid), dim3(256), 0, sm, a);
     hipLaunchKernelGGL(k_map_general_list<false>, dim3(2048), dim3(256), 0, sm, a);     // grid-stride over a list whose length only the device knows
-    if (int s = scan_excl(ctx, a.tile_calls, cb, (int64_t)grid, S[6])) return s;
-    if (int s = scan_excl(ctx, a.tile_text, tb, (int64_t)grid, S[6])) return s;
+    if (int s = scan_excl(ctx, a.tile_calls, cb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
+    if (int s = scan_excl(ctx, a.tile_text, tb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
     uint32_t last[2], n_listed = 0;
     if (space == PHZ_DEVICE) {
         // device-resident outputs already exist at their capacity: nothing on the host has to know the totals before the emit

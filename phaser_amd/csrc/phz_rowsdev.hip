@@ -47,8 +47,6 @@ constexpr int SEG_SMALL = 32, SEG_MID = 256, SEG_LDS = 2048;       // read-set s
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
 constexpr unsigned long long NONE64 = ~0ull;
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 // separator-joined string pool: item i = b[off[i] .. off[i+1] - 1)
 struct PoolD {
     const uint32_t *off;
@@ -1918,12 +1916,6 @@ int up(phz_ctx *ctx, DevBuf &b, const void *src, size_t bytes) {
     return PHZ_OK;
 }
 template <class T> T *P(DevBuf &b) { return (T *)b.p; }
-// reserve a list of (buffer, bytes); the first failure ends it
-struct Rsv { DevBuf &b; size_t bytes; };
-int reserve_all(phz_ctx *ctx, std::initializer_list<Rsv> list) {
-    for (const Rsv &r : list) if (int s = phz_reserve(ctx, r.b, r.bytes)) return s;
-    return PHZ_OK;
-}
 
 // GPU time of the stage = sum over the sync-free sections between two host waits (the host work in between -- scipy, exceptions -- is not GPU time)
 struct Sections {

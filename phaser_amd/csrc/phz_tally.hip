@@ -1054,7 +1054,6 @@ __global__ __launch_bounds__(256) void k_noise(const int32_t *var_count, int64_t
 }
 
 constexpr size_t CNT_BYTES = 128 + (size_t)N_SPREAD * SPREAD_WORDS * 8;
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // HIP-event timing of a stage on the ctx stream; stop() waits for the stage and reports HIP errors
 struct Timer {
@@ -1086,10 +1085,7 @@ int stage_lines(Staging &st, const phz_lines &h, int space, LinesDev *d) {
     return PHZ_OK;
 }
 
-
-// scratch slots of ctx->scratch used by the tally (0 is the AS histogram, 16.. belong to components / K_map)
-enum { T_QBASE = 1, T_TOUCHED, T_CNT_T, T_BASE_T, T_ITEMS, T_COUNTERS, T_GKEYS, T_USEDKEY, T_DEG, T_EOFF, T_EB, T_ESLOT, T_SCAN_TMP, T_USED, T_MISC, T_EA = 19 };
-// results and the read-list buffers live in their own buffers (ctx->tally_buf)
+// results and the read-list buffers live in their own buffers (ctx->tally_buf); per-call scratch: the SC_T_* slots of PhzScratch
 enum { R_CNT = 0, R_FIRST, R_DIST, R_RANK, R_CLS, R_EA, R_EB, R_CELLS, R_LINKED, R_CTO, R_STATS, R_RLCNT, R_RLSTART, R_RLFILL, R_RLTMP, R_RLLIST, R_RLQID, R_A0, R_A1,
        R_LINEQ, R_SORTK, R_SORTV0, R_SORTV1, R_SORTCNT, R_SPQ, R_SPITEM, R_TILEWB, R_TILEM, R_TILEB, R_QSEEN, R_QDUP, R_RLDIRTY, R_COUNT };
 
@@ -1126,27 +1122,33 @@ static int upload_tab(phz_ctx *ctx, const LinesDev *L, int n, F blocks_of, Lines
     return PHZ_OK;
 }
 
+// What every AS-histogram entry point enqueues: the shards staged, their table for k_as_hist's grid uploaded, the kernel (none when no shard has a line).
+// hist / oor_flag are device pointers: where the histogram and the "AS value outside int16" flag live is the caller's business.
+static int enqueue_as_hist(phz_ctx *ctx, Staging &st, const phz_lines *shards, int n_shards, int space, unsigned long long *hist, unsigned int *oor_flag) {
+    if (n_shards <= 0) return PHZ_OK;
+    std::vector<LinesDev> L((size_t)n_shards);
+    for (int i = 0; i < n_shards; i++)
+        if (int s = stage_lines(st, shards[i], space, &L[(size_t)i])) return s;
+    LinesTab T; std::vector<uint32_t> grids;
+    if (int s = upload_tab(ctx, L.data(), n_shards, as_hist_blocks, &T, &grids)) return s;
+    if (grids.back() > 0) hipLaunchKernelGGL(k_as_hist, dim3(grids.back()), dim3(256), 0, ctx->stream, T, hist, oor_flag);
+    return PHZ_OK;
+}
+
 extern "C" int phz_as_histogram(phz_ctx *ctx, const phz_lines *shard, int64_t *hist, int space) {
     PhzEnter phz_guard_(ctx);
     if (!ctx || !shard || !hist) return PHZ_E_ARG;
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     Staging st(ctx);
-    LinesDev L;
-    if (int s = stage_lines(st, *shard, space, &L)) return s;
     unsigned long long *dh = nullptr;
     if (space == PHZ_DEVICE) dh = (unsigned long long *)hist;
     else {
-        if (int s = phz_reserve(ctx, ctx->scratch[0], PHZ_AS_BINS * 8)) return s;
-        dh = (unsigned long long *)ctx->scratch[0].p;
+        if (int s = phz_reserve(ctx, ctx->scratch[SC_AS_HIST], PHZ_AS_BINS * 8)) return s;
+        dh = (unsigned long long *)ctx->scratch[SC_AS_HIST].p;
         PHZ_HIP(ctx, hipMemcpyAsync(dh, hist, PHZ_AS_BINS * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     Timer t(ctx, PHZ_T_ASHIST);
-    if (L.n > 0) {
-        LinesTab T;
-        std::vector<uint32_t> grids;
-        if (int s2 = upload_tab(ctx, &L, 1, as_hist_blocks, &T, &grids)) return s2;
-        hipLaunchKernelGGL(k_as_hist, dim3(grids.back()), dim3(256), 0, ctx->stream, T, dh, (unsigned int *)nullptr);
-    }
+    if (int s = enqueue_as_hist(ctx, st, shard, 1, space, dh, nullptr)) return s;
     PHZ_HIP(ctx, hipGetLastError());
     if (int s = t.stop()) return s;
     if (space == PHZ_HOST) PHZ_HIP(ctx, hipMemcpyAsync(hist, dh, PHZ_AS_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1161,20 +1163,15 @@ extern "C" int phz_as_histogram_batch(phz_ctx *ctx, const phz_lines *shards, int
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     Timer t(ctx, PHZ_T_ASHIST);
     Staging st(ctx);
-    std::vector<LinesDev> L((size_t)n_shards);
-    for (int i = 0; i < n_shards; i++)
-        if (int s = stage_lines(st, shards[i], PHZ_DEVICE, &L[(size_t)i])) return s;
+    DevBuf &flag = ctx->scratch[SC_AS_HIST];          // (the histogram is the caller's: only the out-of-range flag lives here)
     if (n_shards > 0) {
-        LinesTab T;
-        std::vector<uint32_t> grids;
-        if (int s2 = upload_tab(ctx, L.data(), n_shards, as_hist_blocks, &T, &grids)) return s2;
-        if (int s2 = phz_reserve(ctx, ctx->scratch[0], 64)) return s2;
-        PHZ_HIP(ctx, hipMemsetAsync(ctx->scratch[0].p, 0, 4, ctx->stream));
-        if (grids.back() > 0) hipLaunchKernelGGL(k_as_hist, dim3(grids.back()), dim3(256), 0, ctx->stream, T, (unsigned long long *)hist, (unsigned int *)ctx->scratch[0].p);
+        if (int s2 = phz_reserve(ctx, flag, 64)) return s2;
+        PHZ_HIP(ctx, hipMemsetAsync(flag.p, 0, 4, ctx->stream));
     }
+    if (int s = enqueue_as_hist(ctx, st, shards, n_shards, PHZ_DEVICE, (unsigned long long *)hist, (unsigned int *)flag.p)) return s;
     PHZ_HIP(ctx, hipGetLastError());
     unsigned int oor = 0;
-    if (n_shards > 0) PHZ_HIP(ctx, hipMemcpyAsync(&oor, ctx->scratch[0].p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_shards > 0) PHZ_HIP(ctx, hipMemcpyAsync(&oor, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (int s = t.stop()) return s;
     if (oor) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "AS value outside int16");
     return PHZ_OK;
@@ -1187,25 +1184,17 @@ extern "C" int phz_as_histogram_sparse(phz_ctx *ctx, const phz_lines *shards, in
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     Timer t(ctx, PHZ_T_ASHIST);
     Staging st(ctx);
-    std::vector<LinesDev> L((size_t)n_shards);
-    for (int i = 0; i < n_shards; i++)
-        if (int s = stage_lines(st, shards[i], PHZ_DEVICE, &L[(size_t)i])) return s;
-    // scratch[0]: [hist 64 Ki x 8][out-of-range flag, pair count][bins cap x 4][counts cap x 8]; the host image of the tail in h_scalars
+    // SC_AS_HIST: [hist 64 Ki x 8][out-of-range flag, pair count][bins cap x 4][counts cap x 8]; the host image of the tail in h_scalars
     const size_t tail = 16 + (size_t)cap * 12;
-    if (int s2 = phz_reserve(ctx, ctx->scratch[0], PHZ_AS_BINS * 8 + tail)) return s2;
+    if (int s2 = phz_reserve(ctx, ctx->scratch[SC_AS_HIST], PHZ_AS_BINS * 8 + tail)) return s2;
     if (int s2 = phz_reserve_host(ctx, ctx->h_scalars, tail)) return s2;
-    char *d = (char *)ctx->scratch[0].p;
+    char *d = (char *)ctx->scratch[SC_AS_HIST].p;
     unsigned long long *hist = (unsigned long long *)d;
     unsigned int *flags = (unsigned int *)(d + PHZ_AS_BINS * 8);
     int32_t *d_bins = (int32_t *)(d + PHZ_AS_BINS * 8 + 16);
     unsigned long long *d_counts = (unsigned long long *)(d + PHZ_AS_BINS * 8 + 16 + (size_t)cap * 4);
     PHZ_HIP(ctx, hipMemsetAsync(d, 0, PHZ_AS_BINS * 8 + 16, ctx->stream));
-    if (n_shards > 0) {
-        LinesTab T;
-        std::vector<uint32_t> grids;
-        if (int s2 = upload_tab(ctx, L.data(), n_shards, as_hist_blocks, &T, &grids)) return s2;
-        if (grids.back() > 0) hipLaunchKernelGGL(k_as_hist, dim3(grids.back()), dim3(256), 0, ctx->stream, T, hist, flags);
-    }
+    if (int s = enqueue_as_hist(ctx, st, shards, n_shards, PHZ_DEVICE, hist, flags)) return s;
     hipLaunchKernelGGL(k_hist_compact, dim3(PHZ_AS_BINS / 1024), dim3(1024), 0, ctx->stream, (const unsigned long long *)hist, cap, d_bins, d_counts, (int32_t *)(flags + 1));
     PHZ_HIP(ctx, hipGetLastError());
     PHZ_HIP(ctx, hipMemcpyAsync(ctx->h_scalars.p, flags, tail, hipMemcpyDeviceToHost, ctx->stream));
@@ -1331,282 +1320,301 @@ extern "C" int phz_as_cutoff_enqueue(phz_ctx *ctx, const phz_lines *shards, int 
     if (!ctx || (!shards && n_shards) || n_shards < 0 || !dev_out) return PHZ_E_ARG;
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     Staging st(ctx);
-    std::vector<LinesDev> L((size_t)n_shards);
-    for (int i = 0; i < n_shards; i++)
-        if (int s = stage_lines(st, shards[i], PHZ_DEVICE, &L[(size_t)i])) return s;
-    if (int s2 = phz_reserve(ctx, ctx->scratch[0], PHZ_AS_BINS * 8 + 16)) return s2;
-    char *d = (char *)ctx->scratch[0].p;
+    if (int s2 = phz_reserve(ctx, ctx->scratch[SC_AS_HIST], PHZ_AS_BINS * 8 + 16)) return s2;
+    char *d = (char *)ctx->scratch[SC_AS_HIST].p;
     unsigned long long *hist = (unsigned long long *)d;
     unsigned int *flags = (unsigned int *)(d + PHZ_AS_BINS * 8);
     PHZ_HIP(ctx, hipMemsetAsync(d, 0, PHZ_AS_BINS * 8 + 16, ctx->stream));
-    if (n_shards > 0) {
-        LinesTab T;
-        std::vector<uint32_t> grids;
-        if (int s2 = upload_tab(ctx, L.data(), n_shards, as_hist_blocks, &T, &grids)) return s2;
-        if (grids.back() > 0) hipLaunchKernelGGL(k_as_hist, dim3(grids.back()), dim3(256), 0, ctx->stream, T, hist, flags);
-    }
+    if (int s = enqueue_as_hist(ctx, st, shards, n_shards, PHZ_DEVICE, hist, flags)) return s;
     static_assert(PHZ_AS_BINS == 65536, "k_as_percentile: 1024 threads x 64 bins");
     hipLaunchKernelGGL(k_as_percentile, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)hist, (const unsigned int *)flags, q_percent / 100.0, dev_out);
     PHZ_HIP(ctx, hipGetLastError());
     return PHZ_OK;
 }
 
-extern "C" int phz_tally(phz_ctx *ctx, const phz_lines *shards, int n_shards, int64_t nv, const uint8_t *a0, const uint8_t *a1,
-                         int64_t n_qid, int n_bams, phz_tally_sizes *sizes, int space) {
-    PhzEnter phz_guard_(ctx);
-    if (!ctx || (!shards && n_shards) || !sizes || nv < 0 || n_qid < 0 || n_shards < 0 || n_bams < 1) return PHZ_E_ARG;
-    if (nv >= (1ll << 28)) return phz_fail(ctx, PHZ_E_ARG, "more than 2^28 variants in one call");
-    if (n_qid >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "more than 2^31 QNAME ids in one call");
-    if (2 * nv * n_bams >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "variants x BAMs exceeds the read-list key space");
-    PHZ_HIP(ctx, hipSetDevice(ctx->device));
-    memset(sizes, 0, sizeof(*sizes));
-    Staging st(ctx);
-    std::vector<LinesDev> L((size_t)n_shards);
-    int64_t total = 0;
-    for (int b = 0; b < n_shards; b++) {
-        if (shards[b].bam_index < 0 || shards[b].bam_index >= n_bams) return phz_fail(ctx, PHZ_E_ARG, "bam_index outside [0, n_bams)");
-        if (shards[b].var_base < 0 || shards[b].qid_base < 0) return phz_fail(ctx, PHZ_E_ARG, "negative base");
-        if (int s = stage_lines(st, shards[b], space, &L[b])) return s;
-        L[b].line_base = total;
-        total += L[b].n;
-    }
-    if (total >= (1ll << 32) - 16) return phz_fail(ctx, PHZ_E_ARG, "more than 2^32 call lines in one call");
-    // variants of every shard's chromosome: up to the next chromosome's first variant (shards of a chromosome share var_base)
-    for (int b = 0; b < n_shards; b++) {
-        int64_t end = nv;
-        for (int c = 0; c < n_shards; c++)
-            if (L[c].var_base > L[b].var_base && L[c].var_base < end) end = L[c].var_base;
-        if (L[b].var_base > nv) return phz_fail(ctx, PHZ_E_ARG, "var_base beyond the variant space");
-        L[b].nv_chrom = (int32_t)(end - L[b].var_base);
-    }
-    const size_t NV = (size_t)(nv ? nv : 1), NQ = (size_t)(n_qid ? n_qid : 1), TOT = (size_t)(total ? total : 1);
-    const size_t NRL = NV * 2 * (size_t)n_bams;
-    const size_t QWORDS = (NQ + 31) / 32 + (size_t)QW / 32, RLWORDS = (NRL + 31) / 32;      // (+ the LDS window of k_line, which may reach past the last id)
-    if (ctx->tally_buf.size() < (size_t)R_COUNT) ctx->tally_buf.resize(R_COUNT);
-    DevBuf *R = ctx->tally_buf.data();
-    DevBuf *S = ctx->scratch;
-    const uint8_t *d_a0, *d_a1;
-    if (space == PHZ_DEVICE) { d_a0 = a0; d_a1 = a1; }
-    else {
-        if (int s = phz_reserve(ctx, R[R_A0], NV)) return s;
-        if (int s = phz_reserve(ctx, R[R_A1], NV)) return s;
-        if (nv) {
-            PHZ_HIP(ctx, hipMemcpyAsync(R[R_A0].p, a0, (size_t)nv, hipMemcpyHostToDevice, ctx->stream));
-            PHZ_HIP(ctx, hipMemcpyAsync(R[R_A1].p, a1, (size_t)nv, hipMemcpyHostToDevice, ctx->stream));
-        }
-        d_a0 = (const uint8_t *)R[R_A0].p; d_a1 = (const uint8_t *)R[R_A1].p;
-    }
-#define RSV(buf, bytes) do { if (int s_ = phz_reserve(ctx, buf, (bytes))) return s_; } while (0)
+namespace {
+// What one phz_tally call knows.  Its stage functions are the sections of the pass in stream order, each named after what it enqueues; a host wait is the last thing
+// of the section that has one (WAIT in its comment), and what is read back there stays here for the sections after it.
+struct TallyPass {
+    phz_ctx *ctx; hipStream_t sm; DevBuf *R, *S; Staging st;
+    const int64_t nv, n_qid; const int n_shards, n_bams; int64_t total = 0;          // (total: call lines of all shards)
+    size_t NV, NQ, TOT = 1, NRL, QWORDS, RLWORDS, NT = 1; std::vector<LinesDev> L;
     // tiles of the per-line stages (k_line and k_tile: TL lines each) and variant blocks of k_colscan (TWT variants each), over the shard table
-    LinesTab TT, TC;
-    TT.L = nullptr; TT.blk0 = nullptr; TT.n = 0; TC = TT;
-    std::vector<uint32_t> gt, gc;
-    if (n_shards > 0) {
-        if (int s2 = upload_tab(ctx, L.data(), n_shards, [](const LinesDev &l) { return (unsigned)((l.n + TL - 1) / TL); }, &TT, &gt, 0, 2)) return s2;
-        if (int s2 = upload_tab(ctx, L.data(), n_shards, [](const LinesDev &l) { return (unsigned)((l.nv_chrom + TWT - 1) / TWT); }, &TC, &gc, 1, 2)) return s2;
+    LinesTab TT, TC; unsigned grid_t = 0, grid_c = 0;
+    const uint8_t *d_a0 = nullptr, *d_a1 = nullptr;
+    // typed views of the buffers (reserve_and_clear; tab / used / usedkey: pair_table, which sizes them)
+    int32_t *d_cnt, *d_dist, *rl_qid, *tile_wb; unsigned long long *d_first, *d_rank, *counters, *prof = nullptr; uint8_t *d_cls; uint16_t *tile_m;
+    uint32_t *line_q, *rl_cnt, *rl_start, *rl_fill, *rl_list, *qcount, *touched, *cnt_t, *base_t, *counters32, *deg, *eoff, *dirty_list, *big_list, *tile_b, *q_seen, *q_dup, *rl_dirty, *sp_q;
+    uint64_t *rl_tmp, *items, *sp_item;
+    uint32_t *tab = nullptr, *used = nullptr; uint64_t *usedkey = nullptr; uint64_t cap = 0;
+    const bool profiling = getenv("PHZ_TALLY_PROFILE") != nullptr;
+    // the counter block (see k_pairs) as last read back: at "lines and tiles", then once per attempt of "pair table"
+    std::vector<unsigned long long> h_counters = std::vector<unsigned long long>(CNT_BYTES / 8, 0ull);
+    int64_t n_kept = 0, n_dirty = 0;          // read at "lines and tiles"
+    int64_t n_complete = 0, nt = 0, n_spill = 0;          // item slots of the tiles; QNAMEs whose lines straddle tiles (one group each, built from the spilled lines); spilled lines
+    int64_t ne = 0; uint32_t n_big = 0, n_rl = 0;          // read at "pair table": edges, dirty read lists beyond the LDS stage, read-list entries
+
+    TallyPass(phz_ctx *c, int64_t nv_, int64_t n_qid_, int n_shards_, int n_bams_)
+        : ctx(c), sm(c->stream), S(c->scratch), st(c), nv(nv_), n_qid(n_qid_), n_shards(n_shards_), n_bams(n_bams_), NV((size_t)(nv_ ? nv_ : 1)), NQ((size_t)(n_qid_ ? n_qid_ : 1)),
+          NRL(NV * 2 * (size_t)n_bams_), QWORDS((NQ + 31) / 32 + (size_t)QW / 32), RLWORDS((NRL + 31) / 32), L((size_t)n_shards_) {      // (QWORDS: + the LDS window of k_line, which may reach past the last id)
+        if (c->tally_buf.size() < (size_t)R_COUNT) c->tally_buf.resize(R_COUNT);
+        R = c->tally_buf.data();
+        TT.L = nullptr; TT.blk0 = nullptr; TT.n = 0; TC = TT;
     }
-    const unsigned grid_t = n_shards > 0 ? gt.back() : 0u, grid_c = n_shards > 0 ? gc.back() : 0u;
-    const size_t NT = grid_t ? grid_t : 1;
-    RSV(R[R_CNT], NV * 12); RSV(R[R_FIRST], NV * 8); RSV(R[R_DIST], NV * 12); RSV(R[R_RANK], NV * 8); RSV(R[R_CLS], TOT); RSV(R[R_LINEQ], TOT * 4);
-    RSV(R[R_RLCNT], NRL * 4); RSV(R[R_RLSTART], (NRL + 1) * 4); RSV(R[R_RLTMP], TOT * 8); RSV(R[R_RLLIST], TOT * 4); RSV(R[R_RLQID], TOT * 4);
-    RSV(R[R_SPQ], TOT * 4); RSV(R[R_SPITEM], TOT * 8);
-    RSV(R[R_TILEWB], NT * 4); RSV(R[R_TILEM], NT * (TWT * 3) * 2); RSV(R[R_TILEB], NT * (TWT * 2) * 4);
-    RSV(R[R_QSEEN], QWORDS * 4); RSV(R[R_QDUP], QWORDS * 4); RSV(R[R_RLDIRTY], RLWORDS * 4);
-    RSV(S[T_TOUCHED], TOT * 4); RSV(S[T_CNT_T], (TOT + 1) * 4); RSV(S[T_BASE_T], (TOT + 1) * 4); RSV(S[T_ITEMS], (2 * TOT + (size_t)(n_shards + 1) * TL) * 8); RSV(S[T_COUNTERS], CNT_BYTES);
-    RSV(S[T_DEG], NV * 4); RSV(S[T_EOFF], (NV + 1) * 4); RSV(S[T_MISC], std::max(NRL, (size_t)1) * 8 + 64);
-    hipStream_t sm = ctx->stream;
-    {   // two arrays are persistent and all zero between calls: the spilled-line counter / fill cursor per QNAME (k_group_plan and k_groups return it to
+    template <class T> T *res(int slot) const { return (T *)R[slot].p; }
+    template <class T> T *scr(int slot) const { return (T *)S[slot].p; }
+    unsigned long long spread_sum(int k) const { unsigned long long t = 0; for (int c = 0; c < N_SPREAD; c++) t += h_counters[16 + c * SPREAD_WORDS + k]; return t; }
+
+    // ---- the limits of the key spaces, the shards' arrays and the two allele columns staged, the shard tables of the line tiles and the variant blocks uploaded
+    int check_and_stage(const phz_lines *shards, const uint8_t *a0, const uint8_t *a1, int space) {
+        if (nv >= (1ll << 28)) return phz_fail(ctx, PHZ_E_ARG, "more than 2^28 variants in one call");
+        if (n_qid >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "more than 2^31 QNAME ids in one call");
+        if (2 * nv * n_bams >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "variants x BAMs exceeds the read-list key space");
+        PHZ_HIP(ctx, hipSetDevice(ctx->device));
+        for (int b = 0; b < n_shards; b++) {
+            if (shards[b].bam_index < 0 || shards[b].bam_index >= n_bams) return phz_fail(ctx, PHZ_E_ARG, "bam_index outside [0, n_bams)");
+            if (shards[b].var_base < 0 || shards[b].qid_base < 0) return phz_fail(ctx, PHZ_E_ARG, "negative base");
+            if (int s = stage_lines(st, shards[b], space, &L[b])) return s;
+            L[b].line_base = total;
+            total += L[b].n;
+        }
+        if (total >= (1ll << 32) - 16) return phz_fail(ctx, PHZ_E_ARG, "more than 2^32 call lines in one call");
+        TOT = (size_t)(total ? total : 1);
+        // variants of every shard's chromosome: up to the next chromosome's first variant (shards of a chromosome share var_base)
+        for (int b = 0; b < n_shards; b++) {
+            int64_t end = nv;
+            for (int c = 0; c < n_shards; c++)
+                if (L[c].var_base > L[b].var_base && L[c].var_base < end) end = L[c].var_base;
+            if (L[b].var_base > nv) return phz_fail(ctx, PHZ_E_ARG, "var_base beyond the variant space");
+            L[b].nv_chrom = (int32_t)(end - L[b].var_base);
+        }
+        if (space == PHZ_DEVICE) { d_a0 = a0; d_a1 = a1; }
+        else {
+            if (int s = reserve_all(ctx, {{R[R_A0], NV}, {R[R_A1], NV}})) return s;
+            if (nv) {
+                PHZ_HIP(ctx, hipMemcpyAsync(R[R_A0].p, a0, (size_t)nv, hipMemcpyHostToDevice, sm));
+                PHZ_HIP(ctx, hipMemcpyAsync(R[R_A1].p, a1, (size_t)nv, hipMemcpyHostToDevice, sm));
+            }
+            d_a0 = res<const uint8_t>(R_A0); d_a1 = res<const uint8_t>(R_A1);
+        }
+        if (n_shards > 0) {
+            std::vector<uint32_t> gt, gc;
+            if (int s2 = upload_tab(ctx, L.data(), n_shards, [](const LinesDev &l) { return (unsigned)((l.n + TL - 1) / TL); }, &TT, &gt, 0, 2)) return s2;
+            if (int s2 = upload_tab(ctx, L.data(), n_shards, [](const LinesDev &l) { return (unsigned)((l.nv_chrom + TWT - 1) / TWT); }, &TC, &gc, 1, 2)) return s2;
+            grid_t = gt.back(); grid_c = gc.back();
+        }
+        NT = grid_t ? grid_t : 1;
+        return PHZ_OK;
+    }
+    // ---- every buffer whose size is known before the pass; the typed views
+    int reserve_and_clear() {
+        if (int s = reserve_all(ctx, {{R[R_CNT], NV * 12}, {R[R_FIRST], NV * 8}, {R[R_DIST], NV * 12}, {R[R_RANK], NV * 8}, {R[R_CLS], TOT}, {R[R_LINEQ], TOT * 4},
+                                      {R[R_RLCNT], NRL * 4}, {R[R_RLSTART], (NRL + 1) * 4}, {R[R_RLTMP], TOT * 8}, {R[R_RLLIST], TOT * 4}, {R[R_RLQID], TOT * 4},
+                                      {R[R_SPQ], TOT * 4}, {R[R_SPITEM], TOT * 8},
+                                      {R[R_TILEWB], NT * 4}, {R[R_TILEM], NT * (TWT * 3) * 2}, {R[R_TILEB], NT * (TWT * 2) * 4},
+                                      {R[R_QSEEN], QWORDS * 4}, {R[R_QDUP], QWORDS * 4}, {R[R_RLDIRTY], RLWORDS * 4},
+                                      {S[SC_T_TOUCHED], TOT * 4}, {S[SC_T_CNT_T], (TOT + 1) * 4}, {S[SC_T_BASE_T], (TOT + 1) * 4}, {S[SC_T_ITEMS], (2 * TOT + (size_t)(n_shards + 1) * TL) * 8},
+                                      {S[SC_T_COUNTERS], CNT_BYTES}, {S[SC_T_DEG], NV * 4}, {S[SC_T_EOFF], (NV + 1) * 4}, {S[SC_T_MISC], std::max(NRL, (size_t)1) * 8 + 64}})) return s;
+        // two arrays are persistent and all zero between calls: the spilled-line counter / fill cursor per QNAME (k_group_plan and k_groups return it to
         // zero) and the fill cursor per read list (k_rl_sort_dirty does).  They are cleared only when (re)allocated -- or after a call that failed half way
         const size_t before = ctx->tally_qcount.cap, before_rl = R[R_RLFILL].cap;
-        RSV(ctx->tally_qcount, NQ * 4); RSV(R[R_RLFILL], NRL * 4);
+        if (int s = reserve_all(ctx, {{ctx->tally_qcount, NQ * 4}, {R[R_RLFILL], NRL * 4}})) return s;
         if (ctx->tally_qcount.cap != before || ctx->tally_dirty) PHZ_HIP(ctx, hipMemsetAsync(ctx->tally_qcount.p, 0, ctx->tally_qcount.cap, sm));
         if (R[R_RLFILL].cap != before_rl || ctx->tally_dirty) PHZ_HIP(ctx, hipMemsetAsync(R[R_RLFILL].p, 0, R[R_RLFILL].cap, sm));
+        d_cnt = res<int32_t>(R_CNT); d_dist = res<int32_t>(R_DIST); d_first = res<unsigned long long>(R_FIRST); d_rank = res<unsigned long long>(R_RANK); d_cls = res<uint8_t>(R_CLS);
+        line_q = res<uint32_t>(R_LINEQ); rl_cnt = res<uint32_t>(R_RLCNT); rl_start = res<uint32_t>(R_RLSTART); rl_fill = res<uint32_t>(R_RLFILL); rl_list = res<uint32_t>(R_RLLIST);
+        rl_tmp = res<uint64_t>(R_RLTMP); rl_qid = res<int32_t>(R_RLQID); sp_q = res<uint32_t>(R_SPQ); sp_item = res<uint64_t>(R_SPITEM);
+        tile_wb = res<int32_t>(R_TILEWB); tile_m = res<uint16_t>(R_TILEM); tile_b = res<uint32_t>(R_TILEB); q_seen = res<uint32_t>(R_QSEEN); q_dup = res<uint32_t>(R_QDUP); rl_dirty = res<uint32_t>(R_RLDIRTY);
+        qcount = (uint32_t *)ctx->tally_qcount.p; touched = scr<uint32_t>(SC_T_TOUCHED); cnt_t = scr<uint32_t>(SC_T_CNT_T); base_t = scr<uint32_t>(SC_T_BASE_T); items = scr<uint64_t>(SC_T_ITEMS);
+        counters = scr<unsigned long long>(SC_T_COUNTERS); counters32 = (uint32_t *)(counters + 8);          // see k_pairs
+        deg = scr<uint32_t>(SC_T_DEG); eoff = scr<uint32_t>(SC_T_EOFF); dirty_list = scr<uint32_t>(SC_T_MISC); big_list = dirty_list + NRL;
+        return PHZ_OK;
     }
-    int32_t *d_cnt = (int32_t *)R[R_CNT].p, *d_dist = (int32_t *)R[R_DIST].p;
-    unsigned long long *d_first = (unsigned long long *)R[R_FIRST].p, *d_rank = (unsigned long long *)R[R_RANK].p;
-    uint8_t *d_cls = (uint8_t *)R[R_CLS].p;
-    uint32_t *line_q = (uint32_t *)R[R_LINEQ].p;
-    uint32_t *rl_cnt = (uint32_t *)R[R_RLCNT].p, *rl_start = (uint32_t *)R[R_RLSTART].p, *rl_fill = (uint32_t *)R[R_RLFILL].p, *rl_list = (uint32_t *)R[R_RLLIST].p;
-    uint64_t *rl_tmp = (uint64_t *)R[R_RLTMP].p;
-    int32_t *rl_qid = (int32_t *)R[R_RLQID].p;
-    uint32_t *qcount = (uint32_t *)ctx->tally_qcount.p;
-    uint32_t *touched = (uint32_t *)S[T_TOUCHED].p, *cnt_t = (uint32_t *)S[T_CNT_T].p, *base_t = (uint32_t *)S[T_BASE_T].p;
-    uint64_t *items = (uint64_t *)S[T_ITEMS].p;
-    unsigned long long *counters = (unsigned long long *)S[T_COUNTERS].p;      // see k_pairs
-    uint32_t *counters32 = (uint32_t *)(counters + 8);
-    uint32_t *deg = (uint32_t *)S[T_DEG].p, *eoff = (uint32_t *)S[T_EOFF].p;
-    uint32_t *dirty_list = (uint32_t *)S[T_MISC].p, *big_list = dirty_list + NRL;
-    int32_t *tile_wb = (int32_t *)R[R_TILEWB].p; uint16_t *tile_m = (uint16_t *)R[R_TILEM].p; uint32_t *tile_b = (uint32_t *)R[R_TILEB].p;
-    uint32_t *q_seen = (uint32_t *)R[R_QSEEN].p, *q_dup = (uint32_t *)R[R_QDUP].p, *rl_dirty = (uint32_t *)R[R_RLDIRTY].p;
-
-    Timer timer(ctx, PHZ_T_TALLY);
-    ctx->tally_dirty = true;           // cleared again when the call completes
-    PHZ_HIP(ctx, hipMemsetAsync(d_cnt, 0, NV * 12, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(d_dist, 0, NV * 12, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(rl_cnt, 0, NRL * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(d_rank, 0xff, NV * 8, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(counters, 0, CNT_BYTES, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(d_first, 0xff, NV * 8, sm));         // unsigned max for atomicMin == -1 as int64 ("none")
-    PHZ_HIP(ctx, hipMemsetAsync(q_seen, 0, QWORDS * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(q_dup, 0, QWORDS * 4, sm));
-    PHZ_HIP(ctx, hipMemsetAsync(rl_dirty, 0, RLWORDS * 4, sm));
-
-    const int single_bam = n_bams <= 1 ? 1 : 0;     // one BAM: every QNAME's read_vars list is owned by that BAM
-    LineOut O;
-    O.a0 = d_a0; O.a1 = d_a1; O.line_cls = d_cls; O.line_q = line_q; O.var_count = d_cnt; O.var_first = d_first; O.rl_cnt = rl_cnt;
-    O.tile_wb = tile_wb; O.tile_m = tile_m; O.q_seen = q_seen; O.q_dup = q_dup; O.rl_dirty = rl_dirty; O.dirty_list = dirty_list;
-    O.counters = counters; O.nb = n_bams; O.prof = nullptr;
-    const bool profiling = getenv("PHZ_TALLY_PROFILE") != nullptr;
-    const unsigned grid_l = grid_t;
-    if (profiling) { RSV(S[20], (size_t)(grid_l + grid_t + 2) * 16); O.prof = (unsigned long long *)S[20].p; PHZ_HIP(ctx, hipMemsetAsync(S[20].p, 0, (size_t)(grid_l + grid_t + 2) * 16, sm)); }
-    if (grid_t) {
-        hipLaunchKernelGGL(k_tile_base, dim3((unsigned)n_shards), dim3(256), 0, sm, TT, tile_wb);
-        hipLaunchKernelGGL(k_line, dim3(grid_l), dim3(LINE_TB), 0, sm, TT, O);
-        ColScan CS; CS.tile_wb = tile_wb; CS.tile_m = tile_m; CS.tile_b = tile_b; CS.var_count = d_cnt; CS.rl_cnt = rl_cnt; CS.nb = n_bams;
-        if (grid_c) hipLaunchKernelGGL(k_colscan, dim3(grid_c), dim3(TWT * CS_PARTS), 0, sm, TC, TT, CS);
+    // ---- the per-call arrays cleared, then the per-line pass, the column scan, the noise sums, the read-list offsets, the per-tile pass.
+    // WAIT 0: the counter block (kept lines, far lines, dirty read lists, spilled lines and their QNAMEs)
+    int lines_and_tiles() {
+        ctx->tally_dirty = true;           // cleared again when the call completes
+        const struct { void *p; int value; size_t bytes; } clear[] = {{d_cnt, 0, NV * 12}, {d_dist, 0, NV * 12}, {rl_cnt, 0, NRL * 4}, {d_rank, 0xff, NV * 8}, {counters, 0, CNT_BYTES},
+            {d_first, 0xff, NV * 8} /* unsigned max for atomicMin == -1 as int64 ("none") */, {q_seen, 0, QWORDS * 4}, {q_dup, 0, QWORDS * 4}, {rl_dirty, 0, RLWORDS * 4}};
+        for (const auto &c : clear) PHZ_HIP(ctx, hipMemsetAsync(c.p, c.value, c.bytes, sm));
+        LineOut O;
+        O.a0 = d_a0; O.a1 = d_a1; O.line_cls = d_cls; O.line_q = line_q; O.var_count = d_cnt; O.var_first = d_first; O.rl_cnt = rl_cnt;
+        O.tile_wb = tile_wb; O.tile_m = tile_m; O.q_seen = q_seen; O.q_dup = q_dup; O.rl_dirty = rl_dirty; O.dirty_list = dirty_list;
+        O.counters = counters; O.nb = n_bams; O.prof = nullptr;
+        if (profiling) {          // (start, end) cycle stamps per workgroup: k_line's, then k_tile's
+            if (int s = phz_reserve(ctx, S[SC_T_PROFILE], (size_t)(2 * grid_t + 2) * 16)) return s;
+            O.prof = prof = scr<unsigned long long>(SC_T_PROFILE); PHZ_HIP(ctx, hipMemsetAsync(prof, 0, (size_t)(2 * grid_t + 2) * 16, sm));
+        }
+        if (grid_t) {
+            hipLaunchKernelGGL(k_tile_base, dim3((unsigned)n_shards), dim3(256), 0, sm, TT, tile_wb);
+            hipLaunchKernelGGL(k_line, dim3(grid_t), dim3(LINE_TB), 0, sm, TT, O);
+            ColScan CS; CS.tile_wb = tile_wb; CS.tile_m = tile_m; CS.tile_b = tile_b; CS.var_count = d_cnt; CS.rl_cnt = rl_cnt; CS.nb = n_bams;
+            if (grid_c) hipLaunchKernelGGL(k_colscan, dim3(grid_c), dim3(TWT * CS_PARTS), 0, sm, TC, TT, CS);
+        }
+        if (nv) hipLaunchKernelGGL(k_noise, dim3(std::min(nblk(nv), 256u)), dim3(256), 0, sm, (const int32_t *)d_cnt, nv, counters + 4);
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, rl_cnt, rl_start, (int64_t)NRL, S[SC_T_SCAN_TMP])) return s;
+        if (grid_t) {
+            TileOut TO;
+            TO.line_cls = d_cls; TO.line_q = line_q; TO.q_dup = q_dup; TO.qcount = qcount; TO.items = items; TO.sp_q = sp_q; TO.sp_item = sp_item; TO.touched = touched;
+            TO.var_rank = d_rank; TO.var_distinct = d_dist; TO.tile_wb = tile_wb; TO.tile_b = tile_b; TO.rl_start = rl_start; TO.rl_dirty = rl_dirty;
+            TO.rl_qid = rl_qid; TO.rl_list = rl_list; TO.rl_cursor = rl_fill; TO.rl_tmp = rl_tmp; TO.counters = counters; TO.nb = n_bams; TO.nv = nv;
+            TO.prof = profiling ? prof + 2 * (size_t)grid_t : nullptr;
+            hipLaunchKernelGGL(k_tile, dim3(grid_t), dim3(TILE_TB), 0, sm, TT, TO);
+        }
+        PHZ_HIP(ctx, hipGetLastError());
+        // (read-backs go to page-locked memory: a copy into a pageable vector is a blocking, staged copy -- PhzMail in phz_internal.h)
+        if (int s = phz_reserve_host(ctx, ctx->mail_host, CNT_BYTES + 64)) return s;
+        PHZ_HIP(ctx, hipMemcpyAsync(ctx->mail_host.p, counters, CNT_BYTES, hipMemcpyDeviceToHost, sm));
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        memcpy(h_counters.data(), ctx->mail_host.p, CNT_BYTES);
+        if (h_counters[13]) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "AS value outside int16");          // (reported by the device-side percentile of a BAM: phz_as_cutoff_enqueue)
+        n_kept = (int64_t)spread_sum(2); n_dirty = (int64_t)h_counters[11];
+        ctx->counters[PHZ_C_FAR_LINES] += (int64_t)h_counters[12]; ctx->counters[PHZ_C_DIRTY_LISTS] += n_dirty;
+        if (profiling) { if (int s = profile_report()) return s; }
+        n_complete = (int64_t)grid_t * TL; nt = (int64_t)(h_counters[10] >> 32); n_spill = (int64_t)(h_counters[10] & 0xFFFFFFFFull);
+        return PHZ_OK;
     }
-    if (nv) hipLaunchKernelGGL(k_noise, dim3(std::min(nblk(nv), 256u)), dim3(256), 0, sm, (const int32_t *)d_cnt, nv, counters + 4);
-    if (int s = gscan_excl<uint32_t, uint32_t>(ctx, rl_cnt, rl_start, (int64_t)NRL, S[T_SCAN_TMP])) return s;
-    uint32_t *sp_q = (uint32_t *)R[R_SPQ].p; uint64_t *sp_item = (uint64_t *)R[R_SPITEM].p;
-    if (grid_t) {
-        TileOut TO;
-        TO.line_cls = d_cls; TO.line_q = line_q; TO.q_dup = q_dup; TO.qcount = qcount; TO.items = items; TO.sp_q = sp_q; TO.sp_item = sp_item; TO.touched = touched;
-        TO.var_rank = d_rank; TO.var_distinct = d_dist; TO.tile_wb = tile_wb; TO.tile_b = tile_b; TO.rl_start = rl_start; TO.rl_dirty = rl_dirty;
-        TO.rl_qid = rl_qid; TO.rl_list = rl_list; TO.rl_cursor = rl_fill; TO.rl_tmp = rl_tmp; TO.counters = counters; TO.nb = n_bams; TO.nv = nv;
-        TO.prof = profiling ? (unsigned long long *)S[20].p + 2 * (size_t)grid_l : nullptr;
-        hipLaunchKernelGGL(k_tile, dim3(grid_t), dim3(TILE_TB), 0, sm, TT, TO);
-    }
-    PHZ_HIP(ctx, hipGetLastError());
-    // (read-backs go to page-locked memory: a copy into a pageable vector is a blocking, staged copy -- PhzMail in phz_internal.h)
-    if (int s = phz_reserve_host(ctx, ctx->mail_host, CNT_BYTES + 64)) return s;
-    std::vector<unsigned long long> h_cnt(CNT_BYTES / 8, 0ull);
-    unsigned long long *h_counters = h_cnt.data();
-    auto spread_sum = [&](int k) { unsigned long long t = 0; for (int c = 0; c < N_SPREAD; c++) t += h_counters[16 + c * SPREAD_WORDS + k]; return t; };
-    PHZ_HIP(ctx, hipMemcpyAsync(ctx->mail_host.p, counters, CNT_BYTES, hipMemcpyDeviceToHost, sm));
-    PHZ_HIP(ctx, hipStreamSynchronize(sm));
-    memcpy(h_counters, ctx->mail_host.p, CNT_BYTES);
-    if (h_counters[13]) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "AS value outside int16");          // (reported by the device-side percentile of a BAM: phz_as_cutoff_enqueue)
-    const int64_t n_kept = (int64_t)spread_sum(2);
-    const int64_t n_dirty = (int64_t)h_counters[11];
-    ctx->counters[PHZ_C_FAR_LINES] += (int64_t)h_counters[12]; ctx->counters[PHZ_C_DIRTY_LISTS] += n_dirty;
-    if (profiling) {
-        std::vector<unsigned long long> pr((size_t)(grid_l + grid_t) * 2);
-        PHZ_HIP(ctx, hipMemcpy(pr.data(), S[20].p, pr.size() * 8, hipMemcpyDeviceToHost));
-        for (int which = 0; which < 2; which++) {
-            const size_t b0 = which ? grid_l : 0, nb_ = which ? grid_t : grid_l;
-            if (!nb_) continue;
+    // PHZ_TALLY_PROFILE: lifetimes and start times of the workgroups of k_line and k_tile, from their cycle stamps (a blocking copy of its own)
+    int profile_report() {
+        std::vector<unsigned long long> pr((size_t)grid_t * 4);
+        PHZ_HIP(ctx, hipMemcpy(pr.data(), prof, pr.size() * 8, hipMemcpyDeviceToHost));
+        for (int which = 0; which < 2 && grid_t; which++) {
+            const size_t b0 = which ? grid_t : 0, nb_ = grid_t;
             unsigned long long t0 = ~0ull, t1 = 0; double sum = 0; unsigned long long mx = 0; std::vector<unsigned long long> d;
             for (size_t b = 0; b < nb_; b++) { const unsigned long long a = pr[2 * (b0 + b)], e = pr[2 * (b0 + b) + 1]; t0 = std::min(t0, a); t1 = std::max(t1, e); sum += (double)(e - a); mx = std::max(mx, e - a); d.push_back(e - a); }
             std::sort(d.begin(), d.end());
             // start-time profile: how many workgroups had started by 10 %, 50 %, 90 % of the kernel's span
             size_t s10 = 0, s50 = 0, s90 = 0; const double span = (double)(t1 - t0);
-            for (size_t b = 0; b < nb_; b++) { const double st = (double)(pr[2 * (b0 + b)] - t0) / span; s10 += st <= 0.1; s50 += st <= 0.5; s90 += st <= 0.9; }
+            for (size_t b = 0; b < nb_; b++) { const double st_ = (double)(pr[2 * (b0 + b)] - t0) / span; s10 += st_ <= 0.1; s50 += st_ <= 0.5; s90 += st_ <= 0.9; }
             fprintf(stderr, "[tally profile] %s: %zu workgroups, span %.1f us, lifetime avg %.2f us median %.2f p99 %.2f max %.2f us, sum %.1f ms -> avg %.0f resident; started by 10/50/90%% of the span: %zu %zu %zu\n",
                     which ? "k_tile" : "k_line", nb_, span / 100.0, sum / nb_ / 100.0, d[nb_ / 2] / 100.0, d[nb_ * 99 / 100] / 100.0, mx / 100.0, sum / 1e5, sum / span, s10, s50, s90);
         }
         fprintf(stderr, "[tally profile] far lines %llu, dirty read lists %lld\n", h_counters[12], (long long)n_dirty);
+        return PHZ_OK;
     }
-    const int64_t n_complete = (int64_t)grid_t * TL;     // item slots of the tiles (groups finished inside their tile, holes in between)
-    const int64_t nt = (int64_t)(h_counters[10] >> 32);  // QNAMEs whose lines straddle tiles: one group each, built from the spilled lines
-    const int64_t n_spill = (int64_t)(h_counters[10] & 0xFFFFFFFFull);
-    if (nt) {
-        hipLaunchKernelGGL(k_group_plan, dim3(nblk(nt)), dim3(256), 0, sm, nt, (const uint32_t *)touched, qcount, cnt_t);
-        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, cnt_t, base_t, nt, S[T_SCAN_TMP])) return s;
-        hipLaunchKernelGGL(k_group_base, dim3(nblk(nt)), dim3(256), 0, sm, nt, (const uint32_t *)touched, (const uint32_t *)base_t, qcount);
-        hipLaunchKernelGGL(k_items_spill, dim3(nblk(n_spill)), dim3(256), 0, sm, n_spill, (const uint32_t *)sp_q, (const uint64_t *)sp_item, qcount, items + n_complete);
-        GroupOut G; G.qcount = qcount; G.items = items + n_complete; G.cnt_t = cnt_t; G.base_t = base_t; G.touched = touched; G.var_rank = d_rank; G.var_distinct = d_dist;
-        G.counters = counters; G.single_bam = single_bam;
-        hipLaunchKernelGGL(k_groups, dim3(nblk(nt)), dim3(256), 0, sm, nt, TT, G);
-    }
-    // the read lists with far lines into line order
-    PHZ_HIP(ctx, hipMemsetAsync(counters32, 0, 16, sm));
-    if (n_dirty) hipLaunchKernelGGL(k_rl_sort_dirty, dim3((unsigned)n_dirty), dim3(256), 0, sm, (const uint32_t *)dirty_list, (const uint32_t *)rl_start, (const uint64_t *)rl_tmp, rl_qid, rl_fill,
-                                    big_list, counters32);
-    // variant pairs.  The table lives in the ctx, sized from the variant count and kept clean by k_edge_final; a pass that overflows it is redone
-    // with a larger one
-    uint64_t cap = 1 << 16;
-    while (cap < 4 * (uint64_t)NV && cap < (1ull << 30)) cap <<= 1;
-    if (ctx->tally_table_cap > cap) cap = ctx->tally_table_cap;          // a sample that needed a larger table keeps it (no overflow + redo per call)
-    int64_t ne = 0;
-    uint32_t h_c32[4] = {0, 0, 0, 0};
-    uint32_t h_tail[2] = {0, 0};
-    for (int attempt = 0;; attempt++) {
-        const size_t old_k = S[T_GKEYS].cap;
-        RSV(S[T_GKEYS], cap * GE_WORDS * 4); RSV(S[T_USED], cap * 4); RSV(S[T_USEDKEY], cap * 8);
-        uint32_t *tab = (uint32_t *)S[T_GKEYS].p;
-        if (S[T_GKEYS].cap != old_k || ctx->tally_table_dirty || attempt > 0) PHZ_HIP(ctx, hipMemsetAsync(tab, 0, S[T_GKEYS].cap, sm));
-        ctx->tally_table_dirty = true;
-        PHZ_HIP(ctx, hipMemsetAsync(counters, 0, 24, sm));              // overflow
-        PHZ_HIP(ctx, hipMemsetAsync(counters + 16, 0, CNT_BYTES - 128, sm));      // spread statistics
-        PHZ_HIP(ctx, hipMemsetAsync(counters + 7, 0, 8, sm));           // used slots
-        PHZ_HIP(ctx, hipMemsetAsync(deg, 0, NV * 4, sm));               // edges per first variant, counted while the slots are claimed
-        const int64_t m_items = n_complete + n_spill;                // the tiles' slots, then one slot per spilled line
-        if (m_items && getenv("PHZ_TALLY_DEBUG")) {
-            hipLaunchKernelGGL(k_pairs<1>, dim3((unsigned)((m_items + PAIR_ITEMS * PAIR_ROUNDS - 1) / (PAIR_ITEMS * PAIR_ROUNDS))), dim3(PAIRS_TB), 0, sm, (const uint64_t *)items, m_items, tab, (uint32_t)(cap - 1), (uint32_t *)S[T_USED].p, (uint64_t *)S[T_USEDKEY].p, deg, counters);
-            hipLaunchKernelGGL(k_pairs<2>, dim3((unsigned)((m_items + PAIR_ITEMS * PAIR_ROUNDS - 1) / (PAIR_ITEMS * PAIR_ROUNDS))), dim3(PAIRS_TB), 0, sm, (const uint64_t *)items, m_items, tab, (uint32_t)(cap - 1), (uint32_t *)S[T_USED].p, (uint64_t *)S[T_USEDKEY].p, deg, counters);
+    // ---- the groups of the QNAMEs whose lines straddle tiles, built from the spilled lines; then the read lists with far lines into line order (no wait)
+    int spilled_groups_and_dirty_lists() {
+        if (nt) {
+            hipLaunchKernelGGL(k_group_plan, dim3(nblk(nt)), dim3(256), 0, sm, nt, (const uint32_t *)touched, qcount, cnt_t);
+            if (int s = gscan_excl<uint32_t, uint32_t>(ctx, cnt_t, base_t, nt, S[SC_T_SCAN_TMP])) return s;
+            hipLaunchKernelGGL(k_group_base, dim3(nblk(nt)), dim3(256), 0, sm, nt, (const uint32_t *)touched, (const uint32_t *)base_t, qcount);
+            hipLaunchKernelGGL(k_items_spill, dim3(nblk(n_spill)), dim3(256), 0, sm, n_spill, (const uint32_t *)sp_q, (const uint64_t *)sp_item, qcount, items + n_complete);
+            GroupOut G; G.qcount = qcount; G.items = items + n_complete; G.cnt_t = cnt_t; G.base_t = base_t; G.touched = touched; G.var_rank = d_rank; G.var_distinct = d_dist;
+            G.counters = counters; G.single_bam = n_bams <= 1 ? 1 : 0;     // one BAM: every QNAME's read_vars list is owned by that BAM
+            hipLaunchKernelGGL(k_groups, dim3(nblk(nt)), dim3(256), 0, sm, nt, TT, G);
         }
-        if (m_items) hipLaunchKernelGGL(k_pairs<0>, dim3((unsigned)((m_items + PAIR_ITEMS * PAIR_ROUNDS - 1) / (PAIR_ITEMS * PAIR_ROUNDS))), dim3(PAIRS_TB), 0, sm, (const uint64_t *)items, m_items, tab,
-                                        (uint32_t)(cap - 1), (uint32_t *)S[T_USED].p, (uint64_t *)S[T_USEDKEY].p, deg, counters);
-        PHZ_HIP(ctx, hipGetLastError());
-        {
+        PHZ_HIP(ctx, hipMemsetAsync(counters32, 0, 16, sm));
+        if (n_dirty) hipLaunchKernelGGL(k_rl_sort_dirty, dim3((unsigned)n_dirty), dim3(256), 0, sm, (const uint32_t *)dirty_list, (const uint32_t *)rl_start, (const uint64_t *)rl_tmp, rl_qid, rl_fill,
+                                        big_list, counters32);
+        return PHZ_OK;
+    }
+    template <int MODE> void launch_pairs(int64_t m_items) {
+        hipLaunchKernelGGL(k_pairs<MODE>, dim3((unsigned)((m_items + PAIR_ITEMS * PAIR_ROUNDS - 1) / (PAIR_ITEMS * PAIR_ROUNDS))), dim3(PAIRS_TB), 0, sm, (const uint64_t *)items, m_items, tab,
+                           (uint32_t)(cap - 1), used, usedkey, deg, counters);
+    }
+    // ---- variant pairs.  The table is the ctx's own buffer (ctx->tally_table: no other entry point writes it), sized from the variant count and left all zero by
+    // k_edge_out: it is cleared only when (re)allocated, after a call that failed half way, and for a retry.  A pass that overflows it is redone with a table four times
+    // larger (PHZ_C_PAIR_REDOS).  WAIT 1, once per attempt: the counter block (overflow, edges, dirty lists beyond the LDS stage) and the read-list total
+    int pair_table() {
+        cap = 1 << 16;
+        while (cap < 4 * (uint64_t)NV && cap < (1ull << 30)) cap <<= 1;
+        if (ctx->tally_table_cap > cap) cap = ctx->tally_table_cap;          // a sample that needed a larger table keeps it (no overflow + redo per call)
+        const int64_t m_items = n_complete + n_spill;                // the tiles' slots, then one slot per spilled line
+        for (int attempt = 0;; attempt++) {
+            DevBuf &table = ctx->tally_table;
+            const size_t old_k = table.cap;
+            if (int s = reserve_all(ctx, {{table, cap * GE_WORDS * 4}, {S[SC_T_USED], cap * 4}, {S[SC_T_USEDKEY], cap * 8}})) return s;
+            tab = (uint32_t *)table.p; used = scr<uint32_t>(SC_T_USED); usedkey = scr<uint64_t>(SC_T_USEDKEY);
+            if (table.cap != old_k || ctx->tally_table_dirty || attempt > 0) PHZ_HIP(ctx, hipMemsetAsync(tab, 0, table.cap, sm));
+            ctx->tally_table_dirty = true;
+            PHZ_HIP(ctx, hipMemsetAsync(counters, 0, 24, sm));              // overflow
+            PHZ_HIP(ctx, hipMemsetAsync(counters + 16, 0, CNT_BYTES - 128, sm));      // spread statistics
+            PHZ_HIP(ctx, hipMemsetAsync(counters + 7, 0, 8, sm));           // used slots
+            PHZ_HIP(ctx, hipMemsetAsync(deg, 0, NV * 4, sm));               // edges per first variant, counted while the slots are claimed
+            if (m_items && getenv("PHZ_TALLY_DEBUG")) { launch_pairs<1>(m_items); launch_pairs<2>(m_items); }
+            if (m_items) launch_pairs<0>(m_items);
+            PHZ_HIP(ctx, hipGetLastError());
             PhzMail mail(ctx);
             const int m0 = mail.add(counters, CNT_BYTES), m1 = mail.add(rl_start + NRL, 4);       // (counters32 is part of the counter block)
             if (int s = mail.send()) return s;
             PHZ_HIP(ctx, hipStreamSynchronize(sm));
-            memcpy(h_counters, mail.at<char>(m0), CNT_BYTES);
-            memcpy(h_c32, (const char *)mail.at<char>(m0) + 64, 16);
-            h_tail[1] = *mail.at<uint32_t>(m1);
+            memcpy(h_counters.data(), mail.at<char>(m0), CNT_BYTES);
+            n_big = ((const uint32_t *)(mail.at<char>(m0) + 64))[1];
+            n_rl = *mail.at<uint32_t>(m1);
+            if (h_counters[2] == 0) { ne = (int64_t)h_counters[7]; ctx->tally_table_cap = cap; return PHZ_OK; }
+            if (attempt == 4 || cap >= (1ull << 31)) return phz_fail(ctx, PHZ_E_NOMEM, "variant-pair table did not converge");
+            ctx->counters[PHZ_C_PAIR_REDOS]++;
+            cap <<= 2;
         }
-        if (h_counters[2] == 0) { ne = (int64_t)h_counters[7]; ctx->tally_table_cap = cap; break; }
-        if (attempt == 4 || cap >= (1ull << 31)) return phz_fail(ctx, PHZ_E_NOMEM, "variant-pair table did not converge");
-        cap <<= 2;
     }
-    // the dirty read lists beyond the LDS stage: through the device radix sort
-    if (h_c32[1]) {
-        std::vector<uint32_t> big(h_c32[1]), rs((size_t)NRL + 1);
+    // ---- the dirty read lists beyond the LDS stage: through the device radix sort, one list at a time.  TWO BLOCKING COPIES (the list of them, the read-list offsets)
+    int big_read_lists() {
+        if (!n_big) return PHZ_OK;
+        std::vector<uint32_t> big(n_big), rs((size_t)NRL + 1);
         PHZ_HIP(ctx, hipMemcpy(big.data(), big_list, big.size() * 4, hipMemcpyDeviceToHost));
         PHZ_HIP(ctx, hipMemcpy(rs.data(), rl_start, rs.size() * 4, hipMemcpyDeviceToHost));
         size_t longest = 0;
         for (uint32_t e : big) longest = std::max(longest, (size_t)(rs[e + 1] - rs[e]));
-        RSV(R[R_SORTK], longest * 8); RSV(R[R_SORTV0], longest * 4); RSV(R[R_SORTV1], longest * 4);
+        if (int s = reserve_all(ctx, {{R[R_SORTK], longest * 8}, {R[R_SORTV0], longest * 4}, {R[R_SORTV1], longest * 4}})) return s;
         const int hi_bit = 32 + bits_for((uint64_t)(total > 1 ? total - 1 : 1));
         for (uint32_t e : big) {
             const int64_t n = (int64_t)rs[e + 1] - rs[e];
             int where = 0;
-            if (int s = radix_sort_pairs<uint64_t, uint32_t>(ctx, rl_tmp + rs[e], (uint64_t *)R[R_SORTK].p, (uint32_t *)R[R_SORTV0].p, (uint32_t *)R[R_SORTV1].p, n, 32, hi_bit,
-                                                            R[R_SORTCNT], S[T_SCAN_TMP], &where)) return s;
-            hipLaunchKernelGGL(k_rl_take_qid, dim3(nblk(n)), dim3(256), 0, sm, (const uint64_t *)(where ? (uint64_t *)R[R_SORTK].p : rl_tmp + rs[e]), n, rl_qid + rs[e]);
+            if (int s = radix_sort_pairs<uint64_t, uint32_t>(ctx, rl_tmp + rs[e], res<uint64_t>(R_SORTK), res<uint32_t>(R_SORTV0), res<uint32_t>(R_SORTV1), n, 32, hi_bit,
+                                                            R[R_SORTCNT], S[SC_T_SCAN_TMP], &where)) return s;
+            hipLaunchKernelGGL(k_rl_take_qid, dim3(nblk(n)), dim3(256), 0, sm, (const uint64_t *)(where ? res<uint64_t>(R_SORTK) : rl_tmp + rs[e]), n, rl_qid + rs[e]);
         }
+        return PHZ_OK;
     }
-    const size_t NE = (size_t)(ne ? ne : 1);
-    RSV(R[R_EA], NE * 4); RSV(R[R_EB], NE * 4); RSV(R[R_CELLS], NE * 36); RSV(R[R_LINKED], NE); RSV(R[R_CTO], NE * 12); RSV(R[R_STATS], NE * 20);
-    RSV(S[T_EB], NE * 4); RSV(S[T_ESLOT], NE * 4); RSV(S[T_EA], NE * 4);
-    if (ne > 0) {
-        uint32_t *tab = (uint32_t *)S[T_GKEYS].p;
-        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, deg, eoff, nv, S[T_SCAN_TMP])) return s;
-        hipLaunchKernelGGL(k_edge_scatter, dim3(nblk(ne)), dim3(256), 0, sm, (const uint32_t *)S[T_USED].p, (const uint64_t *)S[T_USEDKEY].p, ne, (const uint32_t *)eoff, deg,
-                           (uint32_t *)S[T_EA].p, (uint32_t *)S[T_EB].p, (uint32_t *)S[T_ESLOT].p);
-        hipLaunchKernelGGL(k_edge_sort_big, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)eoff, (uint32_t *)S[T_EB].p, (uint32_t *)S[T_ESLOT].p);
-        hipLaunchKernelGGL(k_edge_out, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint32_t *)eoff, (const uint32_t *)S[T_EA].p, (const uint32_t *)S[T_EB].p,
-                           (const uint32_t *)S[T_ESLOT].p, tab, (int32_t *)R[R_EA].p, (int32_t *)R[R_EB].p, (int32_t *)R[R_CELLS].p, (uint8_t *)R[R_LINKED].p,
-                           (int32_t *)R[R_CTO].p, (int32_t *)R[R_STATS].p);
+    // ---- the used slots into the (a, b)-ordered pair list; every entry of the table read, written out and returned to "empty" (the caller's timer wait follows)
+    int edges() {
+        const size_t NE = (size_t)(ne ? ne : 1);
+        if (int s = reserve_all(ctx, {{R[R_EA], NE * 4}, {R[R_EB], NE * 4}, {R[R_CELLS], NE * 36}, {R[R_LINKED], NE}, {R[R_CTO], NE * 12}, {R[R_STATS], NE * 20},
+                                      {S[SC_T_EB], NE * 4}, {S[SC_T_ESLOT], NE * 4}, {S[SC_T_EA], NE * 4}})) return s;
+        if (ne > 0) {
+            uint32_t *e_a = scr<uint32_t>(SC_T_EA), *e_b = scr<uint32_t>(SC_T_EB), *e_slot = scr<uint32_t>(SC_T_ESLOT);
+            if (int s = gscan_excl<uint32_t, uint32_t>(ctx, deg, eoff, nv, S[SC_T_SCAN_TMP])) return s;
+            hipLaunchKernelGGL(k_edge_scatter, dim3(nblk(ne)), dim3(256), 0, sm, (const uint32_t *)used, (const uint64_t *)usedkey, ne, (const uint32_t *)eoff, deg, e_a, e_b, e_slot);
+            hipLaunchKernelGGL(k_edge_sort_big, dim3(nblk(nv)), dim3(256), 0, sm, nv, (const uint32_t *)eoff, e_b, e_slot);
+            hipLaunchKernelGGL(k_edge_out, dim3(nblk(ne)), dim3(256), 0, sm, ne, (const uint32_t *)eoff, (const uint32_t *)e_a, (const uint32_t *)e_b, (const uint32_t *)e_slot, tab,
+                               res<int32_t>(R_EA), res<int32_t>(R_EB), res<int32_t>(R_CELLS), res<uint8_t>(R_LINKED), res<int32_t>(R_CTO), res<int32_t>(R_STATS));
+        }
+        PHZ_HIP(ctx, hipGetLastError());
+        return PHZ_OK;
     }
-    PHZ_HIP(ctx, hipGetLastError());
-    if (int s = timer.stop()) return s;
-#undef RSV
-    ctx->tally_dirty = false; ctx->tally_table_dirty = false;
-    ctx->tally_gen++;
-    auto &T = ctx->tally;
-    T.nv = nv; T.nb = n_bams; T.n_lines = total; T.n_kept = n_kept; T.n_edges = ne; T.n_rl = (int64_t)h_tail[1];
-    T.var_count = d_cnt; T.var_distinct = d_dist; T.var_first = (int64_t *)d_first; T.var_rank = (uint64_t *)d_rank; T.line_cls = d_cls;
-    T.ea = (int32_t *)R[R_EA].p; T.eb = (int32_t *)R[R_EB].p; T.cells = (int32_t *)R[R_CELLS].p; T.linked = (uint8_t *)R[R_LINKED].p;
-    T.cto = (int32_t *)R[R_CTO].p; T.stats = (int32_t *)R[R_STATS].p;
-    T.rl_start = rl_start; T.rl_qid = rl_qid; T.rl_list = rl_list;
-    sizes->n_lines = total; sizes->n_kept = T.n_kept; sizes->n_edges = ne; sizes->n_read_list = T.n_rl;
-    sizes->n_items = (int64_t)spread_sum(0); sizes->pair_events = (int64_t)spread_sum(1);
-    sizes->noise_match = (int64_t)h_counters[4]; sizes->noise_mismatch = (int64_t)h_counters[5];
-    ctx->counters[PHZ_C_LINES] += total; ctx->counters[PHZ_C_ITEMS] += sizes->n_items; ctx->counters[PHZ_C_PAIR_EVENTS] += sizes->pair_events;
-    ctx->counters[PHZ_C_EDGES] += ne;
+    // ---- the pass is complete: the persistent arrays are clean again, the results become the resident tally of the ctx
+    void publish(phz_tally_sizes *sizes) {
+        ctx->tally_dirty = false; ctx->tally_table_dirty = false; ctx->tally_gen++;
+        auto &T = ctx->tally;
+        T.nv = nv; T.nb = n_bams; T.n_lines = total; T.n_kept = n_kept; T.n_edges = ne; T.n_rl = (int64_t)n_rl;
+        T.var_count = d_cnt; T.var_distinct = d_dist; T.var_first = (int64_t *)d_first; T.var_rank = (uint64_t *)d_rank; T.line_cls = d_cls;
+        T.ea = res<int32_t>(R_EA); T.eb = res<int32_t>(R_EB); T.cells = res<int32_t>(R_CELLS); T.linked = res<uint8_t>(R_LINKED); T.cto = res<int32_t>(R_CTO); T.stats = res<int32_t>(R_STATS);
+        T.rl_start = rl_start; T.rl_qid = rl_qid; T.rl_list = rl_list;
+        sizes->n_lines = total; sizes->n_kept = T.n_kept; sizes->n_edges = ne; sizes->n_read_list = T.n_rl;
+        sizes->n_items = (int64_t)spread_sum(0); sizes->pair_events = (int64_t)spread_sum(1);
+        sizes->noise_match = (int64_t)h_counters[4]; sizes->noise_mismatch = (int64_t)h_counters[5];
+        ctx->counters[PHZ_C_LINES] += total; ctx->counters[PHZ_C_ITEMS] += sizes->n_items; ctx->counters[PHZ_C_PAIR_EVENTS] += sizes->pair_events; ctx->counters[PHZ_C_EDGES] += ne;
+    }
+};
+}  // namespace
+
+// The sections of a pass; its host waits: after the line / tile stage, per attempt of the pair table (one, unless the table overflowed), the timer's at the end
+extern "C" int phz_tally(phz_ctx *ctx, const phz_lines *shards, int n_shards, int64_t nv, const uint8_t *a0, const uint8_t *a1,
+                         int64_t n_qid, int n_bams, phz_tally_sizes *sizes, int space) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || (!shards && n_shards) || !sizes || nv < 0 || n_qid < 0 || n_shards < 0 || n_bams < 1) return PHZ_E_ARG;
+    memset(sizes, 0, sizeof(*sizes));
+    TallyPass P(ctx, nv, n_qid, n_shards, n_bams);
+    if (int s = P.check_and_stage(shards, a0, a1, space)) return s;
+    if (int s = P.reserve_and_clear()) return s;
+    Timer timer(ctx, PHZ_T_TALLY);
+    if (int s = P.lines_and_tiles()) return s;                         // wait 0
+    if (int s = P.spilled_groups_and_dirty_lists()) return s;
+    if (int s = P.pair_table()) return s;                              // wait 1 (per attempt)
+    if (int s = P.big_read_lists()) return s;                          // (blocking copies, rare)
+    if (int s = P.edges()) return s;
+    if (int s = timer.stop()) return s;                                // the timer wait
+    P.publish(sizes);
     return PHZ_OK;
 }
 
@@ -1618,25 +1626,13 @@ extern "C" int phz_tally_fetch(phz_ctx *ctx, const phz_tally_out *out, int space
     auto &T = ctx->tally;
     const hipMemcpyKind kind = space == PHZ_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     hipStream_t sm = ctx->stream;
-    auto cp = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (!dst || !bytes) return PHZ_OK;
-        PHZ_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, sm));
-        return PHZ_OK;
-    };
     const size_t nv = (size_t)T.nv, ne = (size_t)T.n_edges;
-    if (int s = cp(out->var_count, T.var_count, nv * 12)) return s;
-    if (int s = cp(out->var_first, T.var_first, nv * 8)) return s;
-    if (int s = cp(out->var_distinct, T.var_distinct, nv * 12)) return s;
-    if (int s = cp(out->var_rank, T.var_rank, nv * 8)) return s;
-    if (int s = cp(out->line_cls, T.line_cls, (size_t)T.n_lines)) return s;
-    if (int s = cp(out->edge_a, T.ea, ne * 4)) return s;
-    if (int s = cp(out->edge_b, T.eb, ne * 4)) return s;
-    if (int s = cp(out->edge_cells, T.cells, ne * 36)) return s;
-    if (int s = cp(out->edge_linked, T.linked, ne)) return s;
-    if (int s = cp(out->edge_cto, T.cto, ne * 12)) return s;
-    if (int s = cp(out->edge_stats, T.stats, ne * 20)) return s;
-    if (int s = cp(out->rl_start, T.rl_start, (nv * 2 * (size_t)T.nb + 1) * 4)) return s;
-    if (int s = cp(out->rl_qid, T.rl_qid, (size_t)T.n_rl * 4)) return s;
+    const struct { void *dst; const void *src; size_t bytes; } parts[] = {
+        {out->var_count, T.var_count, nv * 12}, {out->var_first, T.var_first, nv * 8}, {out->var_distinct, T.var_distinct, nv * 12}, {out->var_rank, T.var_rank, nv * 8},
+        {out->line_cls, T.line_cls, (size_t)T.n_lines}, {out->edge_a, T.ea, ne * 4}, {out->edge_b, T.eb, ne * 4}, {out->edge_cells, T.cells, ne * 36}, {out->edge_linked, T.linked, ne},
+        {out->edge_cto, T.cto, ne * 12}, {out->edge_stats, T.stats, ne * 20}, {out->rl_start, T.rl_start, (nv * 2 * (size_t)T.nb + 1) * 4}, {out->rl_qid, T.rl_qid, (size_t)T.n_rl * 4}};
+    for (const auto &c : parts)
+        if (c.dst && c.bytes) PHZ_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, kind, sm));
     PHZ_HIP(ctx, hipStreamSynchronize(sm));
     return PHZ_OK;
 }
@@ -1663,8 +1659,8 @@ extern "C" int phz_components(phz_ctx *ctx, int64_t nv, int64_t n_edges, const i
     }
     if (int s = st.in(keep, (size_t)n_edges, space, &kp)) return s;
     if (int s = st.out(label, (size_t)nv, space, &lab)) return s;
-    if (int s = phz_reserve(ctx, ctx->scratch[16], (size_t)(nv ? nv : 1) * 4)) return s;
-    int32_t *parent = (int32_t *)ctx->scratch[16].p;
+    if (int s = phz_reserve(ctx, ctx->scratch[SC_UF_PARENT], (size_t)(nv ? nv : 1) * 4)) return s;
+    int32_t *parent = (int32_t *)ctx->scratch[SC_UF_PARENT].p;
     Timer t(ctx, PHZ_T_COMPONENTS);
     if (nv) hipLaunchKernelGGL(k_uf_init, dim3(nblk(nv)), dim3(256), 0, ctx->stream, parent, nv);
     if (n_edges) hipLaunchKernelGGL(k_uf_hook, dim3(nblk(n_edges)), dim3(256), 0, ctx->stream, parent, ea, eb, kp, n_edges);

@@ -919,3 +919,74 @@ def test_copy_as_written_on_later_passes(mapper, monkeypatch):
     for name in OUTPUTS:
         assert first[name] == second[name] == third[name] == fourth[name], name
     compare(first, d)
+
+
+_TALLY_CASE = "opts_isize"          # the smallest committed tally fixture: its pair table is the minimum, 2^16 slots x 64 B = 4 MiB
+
+
+@pytest.fixture(scope="module")
+def small_tally():
+    import gzip
+    import pickle
+    from helpers import genome_from_saved
+    saved = pickle.load(gzip.open(os.path.join(GOLD, "tally", _TALLY_CASE + ".pkl.gz"), "rb"))
+    chroms = list(saved["tally"])
+    nb = 1 + max(b for c in chroms for b, _, _ in saved["tally"][c]["bam_offsets"])
+    return saved, chroms, nb, genome_from_saved(saved, chroms, nb)
+
+
+def _intern_half_a_million_names(mapper):
+    """phz_intern_device on 2^19 distinct 8-byte names and an empty store: its hash table is 2^20 words = 4 MiB, all of them set to 0xff first"""
+    import ctypes as C
+    n = 1 << 19
+    names = torch.from_numpy(np.char.encode(np.char.zfill(np.arange(n).astype(str), 8)).view(np.uint8).copy()).cuda()
+    off = (torch.arange(n + 1, dtype=torch.int64) * 8).to(torch.int32).cuda()
+    qid = torch.empty(n, dtype=torch.int32, device="cuda"); first = torch.empty(n, dtype=torch.int32, device="cuda")
+    n_new = C.c_int64(0)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    torch.cuda.synchronize()
+    ctx = mapper.ctx
+    ctx.check(ctx.lib.phz_intern_device(ctx.h, p(names), p(off), n, None, None, 0, p(qid), p(first), C.byref(n_new)))
+    assert n_new.value == n and torch.equal(qid.cpu(), torch.arange(n, dtype=torch.int32))
+
+
+def _map_indel_reads(mapper):
+    """phz_map_reads_general on the main indel shape (tests/indel_inputs.py): its work list of record indices is a scratch buffer of the ctx"""
+    import indel_inputs as ii
+    from phaser_amd import soa
+    rb, vt = ii.inputs("main")
+    off, ab = vt.allele_pool()
+    calls, _ = mapper.map_general(soa.pack_readbatch(rb).to("cuda"), torch.from_numpy(vt.pos.astype(np.int32)), torch.from_numpy(vt.ref_len), torch.from_numpy(off),
+                                  torch.from_numpy(ab), 10)
+    assert calls.n > 5000
+
+
+@pytest.mark.parametrize("between", ["intern_device", "map_reads_general"])
+def test_tally_after_another_stage_on_the_same_ctx(small_tally, between):
+    """tally, another entry point that uses the ctx's shared scratch, tally again -- on ONE ctx: the second tally gives the fixture's arrays (the equalities of
+    test_emu_tally.test_tally_kernels_reproduce_the_gpu_fixture) and does not redo its variant-pair pass (PHZ_C_PAIR_REDOS does not move): the pair table is
+    the tally's own buffer, so nothing the stage in between writes can be mistaken for its entries."""
+    from phaser_amd import _lib
+    from phaser_amd.mapper import Mapper
+    from test_emu_tally import run_tally
+    saved, chroms, nb, want = small_tally
+    mapper = Mapper(0)          # a ctx of its own: the table has its minimum size and nothing else has touched the scratch
+    ctx = mapper.ctx
+    run_tally(ctx, saved, chroms, nb)
+    redos = ctx.counter(_lib.PHZ_C_PAIR_REDOS)
+    {"intern_device": _intern_half_a_million_names, "map_reads_general": _map_indel_reads}[between](mapper)
+    got, sz = run_tally(ctx, saved, chroms, nb)
+    print("pair-table redos: %d after the first tally, %d after the second" % (redos, ctx.counter(_lib.PHZ_C_PAIR_REDOS)))
+    NV = want["nv"]
+    assert np.array_equal(got["var_count"].reshape(NV, 3), want["var_count"])
+    assert np.array_equal(got["var_first"], want["var_first"])
+    assert np.array_equal(got["var_distinct"].reshape(NV, 3), want["var_distinct"])
+    assert np.array_equal(got["var_rank"], want["var_rank"])
+    assert np.array_equal(got["ea"], want["ea"]) and np.array_equal(got["eb"], want["eb"])
+    assert np.array_equal(got["linked"], want["linked"])
+    assert np.array_equal(got["cto"].reshape(-1, 3), want["cto"])
+    assert np.array_equal(got["stats"].reshape(5, -1), want["stats"])
+    assert np.array_equal(got["rl_start"], want["rl_start"]) and np.array_equal(got["rl_qid"], want["rl_qid"])
+    assert (int(sz.noise_match), int(sz.noise_mismatch)) == want["noise"] and int(sz.n_kept) == want["n_kept"]
+    assert ctx.counter(_lib.PHZ_C_PAIR_REDOS) == redos
+    ctx.close()
