@@ -179,7 +179,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_COUNT = 9 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_COUNT = 10 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -405,6 +405,14 @@ int phz_sam_calls_tsv(const phz_sam *h, int shard, int64_t n_calls, const int32_
  * gt_index -1 when FORMAT has no GT).  *contigs_out: the VCF's contigs, one per line.  Both buffers are released with phz_buf_free. */
 int phz_vcf_lookup(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples, const char *const *samples,
                    int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
+
+/* phaser_annotate's lookups (phaser_annotate.py:302-331 the CADD table, :260-281 the allele-frequency VCF): the same keys, index chunks and scan as
+ * phz_vcf_lookup for ANY bgzipped tab-separated file that keeps the contig in column 1 and the 1-based position in column 2 (the index's own column
+ * configuration is never read), reduced to the caller's choice of columns.  cols[n_cols]: 0-based columns, -1 = the line's last column; a column the line
+ * lacks comes back empty.  *out: one line per matching line in file order, "key" + "\t" + column text for every entry of cols.  No header line is looked
+ * for (a CADD table has none that names samples).  *contigs_out as phz_vcf_lookup.  Both buffers are released with phz_buf_free. */
+int phz_tabix_lines(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_cols, const int32_t *cols,
+                    int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
 
 /* whole BGZF file -> buffer owned by the library (release it with phz_buf_free and nothing else: a large text is an anonymous mapping, not a malloc'd block);
  * PHZ_E_UNSUPPORTED when the file is plain gzip */
@@ -714,6 +722,40 @@ typedef struct {
 } phz_boot_in;
 
 int phz_bootstrap_medians(phz_ctx *ctx, const phz_boot_in *in, double *order_stats, int64_t *sign_counts, double *replicates, int space);
+
+/* K_annot: the pair loops of phaser_annotate (phaser_annotate/phaser_annotate.py:344-403 get_gene_interactions, :225-247 get_interactions and the
+ * annotation test of :426) for every gene of a sample.  Gene g owns the entries [entry_off[g], entry_off[g + 1]): first its n_gw[g] genome-wide-phase
+ * entries, then its read-backed (PG) entries, each list in the reference's order (a variant appears once per matching CADD row).  An entry names a variant,
+ * the mask of the allele indices (bit k = allele k, 1..15) that carry an annotation for (variant, gene), and two flags.  Every variant has two info rows
+ * (genome-wide, read-backed): its two allele indices and the id of its phase block (equal ids = equal blocks).
+ * Output: one record per output row in exactly the reference's order -- genes as given; in a gene the GW x GW pass (a major, b minor, the two entries on
+ * different variants) and then the PG x PG pass (pairs that the first pass did not visit, every variant pair once); in a pair the allele combinations
+ * (0,0), (0,1), (1,0), (1,1) without those that involve allele 0 or an allele outside the masks.
+ * Two calls: rows == NULL counts (*n_rows, *n_pairs); then rows with room for rows_cap >= *n_rows records is filled.  The device holds at most batch_rows
+ * records at a time (0 = PHZ_ANNOT_BATCH_ROWS, at most 2^30): gene ranges are run in batches, PHZ_E_CAPACITY (with a message) only when ONE gene has more rows.
+ * Host arrays only; PHZ_E_ARG when an offset, a variant index or an allele is out of range.  The kernels are timed into PHZ_T_ANNOT. */
+enum { PHZ_ANNOT_BOTH = 1 /* the variant is also in the gene's other list */, PHZ_ANNOT_FIRST = 2 /* PG entry: first entry of its variant in this PG list */ };
+enum { PHZ_ANNOT_BATCH_ROWS = 1 << 24 };
+typedef struct {
+    int64_t n_genes, n_entries, n_vars;
+    const int64_t *entry_off;      /* [n_genes + 1] */
+    const int32_t *n_gw;           /* [n_genes] */
+    const int32_t *entry_var;      /* [n_entries] */
+    const uint16_t *entry_mask;    /* [n_entries] */
+    const uint8_t *entry_flags;    /* [n_entries] */
+    const uint8_t *gw_allele, *pg_allele;      /* [2 n_vars] allele indices 0..15 */
+    const int32_t *gw_block, *pg_block;        /* [n_vars] */
+} phz_annot_in;
+/* bits: 0-3 allele a, 4-7 allele b, 8 trans (0 = cis), 9 the alleles come from the read-backed info rows, 10-11 read_backed + 1 */
+typedef struct { int32_t gene, entry_a, entry_b; uint32_t bits; } phz_annot_rec;
+int phz_annot_pairs(phz_ctx *ctx, const phz_annot_in *in, int64_t batch_rows, phz_annot_rec *rows, int64_t rows_cap, int64_t *n_rows, int64_t *n_pairs,
+                    int32_t *n_batches);
+
+/* Output rows of phaser_annotate (:405-456) from K_annot's records, threaded.  slot_of[entry * 16 + allele] = slot of an annotated (entry, allele), -1 = none;
+ * per slot two texts (byte ranges [off[s], off[s + 1]) of a blob): head = "gene\tname", side = "variant\trsid\tallele\taf\tphred\teffect".  A row is
+ * head[a] \t side[a] \t side[b] \t cis|trans \t read_backed \n.  PHZ_E_ARG when a record names an entry or a slot out of range.  out is malloc'd (phz_buf_free). */
+int phz_annot_rows(const phz_annot_rec *rec, int64_t n_rows, int64_t n_entries, const int32_t *slot_of, int64_t n_slots, const char *head,
+                   const int64_t *head_off, const char *side, const int64_t *side_off, int32_t threads, char **out, int64_t *out_len);
 
 /* Output rows of phaser_gene_ae (:147-163), threaded.  Keys are bam * n_features + feature.  Pools: items followed by '\n'.
  * out is malloc'd (phz_buf_free). */

@@ -19,7 +19,10 @@ CSRC = os.path.join(HERE, "csrc")
 
 PHZ_OK, PHZ_E_ARG, PHZ_E_HIP, PHZ_E_CAPACITY, PHZ_E_UNSUPPORTED, PHZ_E_NOMEM = 0, -1, -2, -3, -4, -5
 PHZ_HOST, PHZ_DEVICE = 0, 1
-PHZ_T_MAP, PHZ_T_ASHIST, PHZ_T_TALLY, PHZ_T_COMPONENTS, PHZ_T_GENES, PHZ_T_INFLATE, PHZ_T_BAMPACK, PHZ_T_ROWS, PHZ_T_BOOT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+PHZ_T_MAP, PHZ_T_ASHIST, PHZ_T_TALLY, PHZ_T_COMPONENTS, PHZ_T_GENES, PHZ_T_INFLATE, PHZ_T_BAMPACK, PHZ_T_ROWS, PHZ_T_BOOT, PHZ_T_ANNOT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+PHZ_T_COUNT = 10
+PHZ_ANNOT_BOTH, PHZ_ANNOT_FIRST = 1, 2
+PHZ_ANNOT_BATCH_ROWS = 1 << 24
 PHZ_C_LINES, PHZ_C_ITEMS, PHZ_C_PAIR_EVENTS, PHZ_C_EDGES, PHZ_C_FAR_LINES, PHZ_C_DIRTY_LISTS, PHZ_C_PAIR_REDOS = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -165,6 +168,12 @@ class phz_boot_in(C.Structure):
                 ("sorted_a", C.c_void_p), ("max_n", C.c_int32), ("bs", C.c_int32), ("k", C.c_int32 * 4), ("seed", C.c_uint64)]
 
 
+class phz_annot_in(C.Structure):
+    _fields_ = [("n_genes", C.c_int64), ("n_entries", C.c_int64), ("n_vars", C.c_int64), ("entry_off", C.c_void_p), ("n_gw", C.c_void_p),
+                ("entry_var", C.c_void_p), ("entry_mask", C.c_void_p), ("entry_flags", C.c_void_p), ("gw_allele", C.c_void_p),
+                ("pg_allele", C.c_void_p), ("gw_block", C.c_void_p), ("pg_block", C.c_void_p)]
+
+
 class phz_vcf_opts(C.Structure):
     _fields_ = [("sample_column", C.c_int32), ("chrom_of_interest", C.c_char_p), ("pass_only", C.c_int32), ("include_indels", C.c_int32),
                 ("chr_prefix", C.c_char_p), ("id_separator", C.c_char_p), ("gw_phase_method", C.c_int32), ("gw_af_field", C.c_char_p),
@@ -285,6 +294,8 @@ SYMBOLS = {
     "phz_bgzf_read": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "phz_vcf_lookup": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "phz_tabix_lines": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_int,
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "phz_buf_free": (None, [C.c_void_p]),
     "phz_bgzf_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
     "phz_bam_write": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(phz_read_batch), C.c_int, C.c_int]),
@@ -324,6 +335,10 @@ SYMBOLS = {
     "phz_gene_rows": (C.c_int, [C.POINTER(phz_gene_rows_in), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "phz_gene_counts": (C.c_int, [C.c_void_p, C.POINTER(phz_gene_work), C.c_void_p, C.c_int]),
     "phz_bootstrap_medians": (C.c_int, [C.c_void_p, C.POINTER(phz_boot_in), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "phz_annot_pairs": (C.c_int, [C.c_void_p, C.POINTER(phz_annot_in), C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_int32)]),
+    "phz_annot_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "phz_vcf_parse": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(phz_vcf_opts), C.POINTER(C.c_void_p)]),
     "phz_vcf_summary": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int64)]),

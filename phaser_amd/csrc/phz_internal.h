@@ -35,6 +35,8 @@ enum PhzScratch {
     SC_BAM_SCAN_TMP = 6, SC_INTERN_TABLE = 7, SC_INTERN_SLOT_OF = 8, SC_INTERN_FIRST = 9, SC_INTERN_RANK = 10, SC_NAMES_LEN = 8, SC_NAMES_PRE = 9,
     // K_inflate: code lengths + cold table part per member
     SC_INFLATE_LENS = 11,
+    // K_annot (phz_annot_pairs): rows per tile, their exclusive scan, the scan's temporary, the records of one batch
+    SC_ANNOT_COUNT = 0, SC_ANNOT_BASE = 1, SC_ANNOT_SCAN_TMP = 2, SC_ANNOT_OUT = 3,
     SC_COUNT = 24
 };
 

@@ -5,6 +5,9 @@
 // With <path>.tbi: the index gives, per key, the chunks of its UCSC bins that end past the linear-index bound of the key's 16 kb window; the chunks
 // of all keys are merged into disjoint spans of virtual offsets, each span's BGZF members are read and inflated on a worker thread, and only the
 // span's lines are scanned.  Without an index: the whole file is inflated (phz_bgzf_read) and scanned.  Both paths report the same lines in file order.
+//
+// phz_tabix_lines (phaser_annotate's CADD table and allele-frequency VCF) is the same lookup with another reduction of a matching line: a caller-chosen
+// list of columns instead of the VCF fields, and no header line to find.
 #include <fcntl.h>
 #include <stdlib.h>
 #include <string.h>
@@ -32,6 +35,8 @@ struct KeyHash { size_t operator()(const Key &k) const { return std::hash<std::s
 struct Ctx {
     std::unordered_map<Key, int64_t, KeyHash> keys;
     std::vector<int32_t> scol;             // VCF column of each mapped sample, -1 = absent from the header
+    const int32_t *cols = nullptr;         // phz_tabix_lines: the columns to report (-1 = the last one) instead of the VCF fields
+    int32_t n_cols = 0;
 };
 
 // one record line -> output line "key\tCHROM\tPOS\tID\tREF\tALT\tgi\tGT...\n" (GT of a column the line lacks: "\x01")
@@ -44,6 +49,15 @@ void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
         f.push_back(line.substr(i, j - i)); i = j + 1;
     }
     out += std::to_string(key);
+    if (C.cols) {
+        for (int32_t k = 0; k < C.n_cols; k++) {
+            const int64_t c = C.cols[k] < 0 ? (int64_t)f.size() - 1 : C.cols[k];
+            out += '\t';
+            if (c >= 0 && (size_t)c < f.size()) out.append(f[(size_t)c]);
+        }
+        out += '\n';
+        return;
+    }
     for (int k = 0; k < 5; k++) { out += '\t'; if ((size_t)k < f.size()) out.append(f[(size_t)k]); }
     int gi = -1;
     if (f.size() > 8) {
@@ -194,15 +208,12 @@ char *to_malloc(const std::string &s) {
     return p;
 }
 
-}  // namespace
-
-extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples,
-                              const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out,
-                              int64_t *contigs_len) {
-    if (!path || n_keys < 0 || n_samples < 0 || !out || !out_len || !contigs_out || !contigs_len || (n_keys && (!contig || !pos)) || (n_samples && !samples))
-        return PHZ_E_ARG;
+// the lookup both entry points share; C.cols set: column mode, no header line is looked for
+int lookup(Ctx &C, const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples, const char *const *samples,
+           int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len) {
+    if (!path || n_keys < 0 || !out || !out_len || !contigs_out || !contigs_len || (n_keys && (!contig || !pos))) return PHZ_E_ARG;
     *out = nullptr; *out_len = 0; *contigs_out = nullptr; *contigs_len = 0;
-    Ctx C;
+    const bool want_header = C.cols == nullptr;
     for (int64_t k = 0; k < n_keys; k++) C.keys.emplace(Key{contig[k], pos[k]}, k);
     const int nt = std::max(1, std::min(threads, 64));
     std::vector<std::string> contigs;
@@ -213,7 +224,7 @@ extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *cons
     // ---- header: the #CHROM line (the index path inflates members from the file start until the line is complete)
     std::string head;
     char *whole_p = nullptr; int64_t whole_n = 0;
-    if (indexed) {
+    if (indexed && want_header) {
         int fd = open(path, O_RDONLY);
         if (fd < 0) return PHZ_E_ARG;
         uint64_t off = 0; std::vector<uint8_t> m; std::string txt;
@@ -227,10 +238,10 @@ extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *cons
             if (!is) break;
         }
         close(fd);
-    } else {
+    } else if (!indexed) {
         if (int st = phz_bgzf_read(path, nt, &whole_p, &whole_n)) return st;
         std::string_view w(whole_p, (size_t)whole_n);
-        size_t a = w.find("#CHROM");
+        const size_t a = want_header ? w.find("#CHROM") : std::string_view::npos;
         if (a != std::string_view::npos) head = std::string(w.substr(a, w.find('\n', a) - a));
     }
     if (!head.empty() && head.back() == '\r') head.pop_back();
@@ -316,4 +327,22 @@ extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *cons
     if (!*out || !*contigs_out) { free(*out); free(*contigs_out); *out = *contigs_out = nullptr; return PHZ_E_NOMEM; }
     *out_len = (int64_t)result.size(); *contigs_len = (int64_t)cs.size();
     return PHZ_OK;
+}
+
+}  // namespace
+
+extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples,
+                              const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out,
+                              int64_t *contigs_len) {
+    if (n_samples < 0 || (n_samples && !samples)) return PHZ_E_ARG;
+    Ctx C;
+    return lookup(C, path, n_keys, contig, pos, n_samples, samples, use_index, threads, out, out_len, contigs_out, contigs_len);
+}
+
+extern "C" int phz_tabix_lines(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_cols, const int32_t *cols,
+                               int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len) {
+    if (n_cols < 1 || !cols) return PHZ_E_ARG;
+    Ctx C;
+    C.cols = cols; C.n_cols = n_cols;
+    return lookup(C, path, n_keys, contig, pos, 0, nullptr, use_index, threads, out, out_len, contigs_out, contigs_len);
 }
