@@ -27,6 +27,7 @@
 // offset, so the call list is in mapper order with no inter-workgroup dependency inside k_map (a
 // decoupled look-back was measured 0.8 ms slower here: tiles finish faster than descriptors travel).
 #include "phz_internal.h"
+#include "phz_lbound.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -329,34 +330,28 @@ __device__ int walk_read(const MapArgs &a, const VarWin &vw, const CigWin &cw, c
 // Insertions follow the reference's keying (key = genome offset - 1 at the I op, looked up SEGMENT-relative): while seg_start is 0
 // that is the last base of the op before the I (found by peeking at the next op); after an N the key lands seg_start bases further
 // on, i.e. in a later run of the same segment (carried forward in two register slots, the later insertion wins).
-// Lower bound over the staged window, branch-free per step: the window is padded with INT_MAX up to MAP_WIN entries, so a probe needs
-// no bounds test, and the number of steps (wave-uniform, computed once per tile from the window length) selects the entry point of a
-// fully unrolled halving chain -- three vector instructions and one LDS read per step, no loop bookkeeping on the scalar unit.
-__device__ __forceinline__ int window_depth(int wlen) {          // steps 2^(d-1) .. 1, then one closing probe: reaches every count <= wlen
-    const int d = wlen > 0 ? 32 - __builtin_clz((unsigned)wlen) : 0;
-    constexpr int dmax = 31 - __builtin_clz((unsigned)MAP_WIN);
-    return d < dmax ? d : dmax;
+// Lower bound over the staged window: window_lower_bound<D> of phz_lbound.h, a fully unrolled chain of D halving steps and a closing probe over a
+// window padded with INT_MAX up to 2^D entries -- five issue slots per probe (LDS read with an immediate offset, wait, subtract, shift, and-or), no
+// compare / select pair (its VCC hazard costs an s_nop per probe) and nothing on the scalar unit between probes.  The depth is a template
+// parameter: a tile belongs to one of a few DEPTH CLASSES by its window length (wave-uniform, computed once per tile), and a search picks its class
+// with one scalar if/else.  (Until round 10 the depth was the entry point of a `switch` with fall-through cases: the compiler turned that ladder
+// into scalar compares, branches and 64-bit mask moves BETWEEN the probes, 25-30 scalar instructions per search on the busier port.)
+// Two classes, from the staged window lengths of the whole-genome sample (profiles/r10/kmap_search_ab.txt: 75 % of the tiles stage at most 64 entries, 25 %
+// 65..128, one in a thousand more): D = 7, whose padding is one round of the 128-thread workgroup, and the full window.  (D = 6 saves three quarters of
+// the tiles one probe but sends the fourth quarter through the ten probes and four padding rounds of the full window: the same instruction total, more LDS
+// traffic; a third class costs the production kernel a spilled vector register -- the first probe of every class is hoisted out of the op loop.)
+#ifndef PHZ_WIN_DSMALL
+#define PHZ_WIN_DSMALL 7
+#endif
+constexpr int WIN_DMAX = 31 - __builtin_clz((unsigned)MAP_WIN);                      // the class of the largest window: 2^WIN_DMAX == MAP_WIN entries
+constexpr int WIN_DSMALL = WIN_DMAX < PHZ_WIN_DSMALL ? WIN_DMAX : PHZ_WIN_DSMALL;    // the class of the typical tile
+static_assert(MAP_WIN >= 2 && MAP_WIN <= 1024 && (MAP_WIN & (MAP_WIN - 1)) == 0, "MAP_WIN: a power of two up to 1024");
+__device__ __forceinline__ int window_depth(int wlen) {          // depth class of a window: the chain reaches every count <= 2^depth >= wlen
+    return wlen <= (1 << WIN_DSMALL) ? WIN_DSMALL : WIN_DMAX;
 }
-__device__ __forceinline__ int lds_lower_bound(const int32_t *w, int depth, int key) {
-    static_assert(MAP_WIN >= 2 && MAP_WIN <= 1024 && (MAP_WIN & (MAP_WIN - 1)) == 0, "MAP_WIN: a power of two up to 1024");
-    int base = 0;
-#define PHZ_LB_STEP(S) base = (w[base + (S) - 1] < key) ? base + (S) : base
-    switch (depth) {
-    default: PHZ_LB_STEP(512); [[fallthrough]];
-    case 9: PHZ_LB_STEP(256); [[fallthrough]];
-    case 8: PHZ_LB_STEP(128); [[fallthrough]];
-    case 7: PHZ_LB_STEP(64); [[fallthrough]];
-    case 6: PHZ_LB_STEP(32); [[fallthrough]];
-    case 5: PHZ_LB_STEP(16); [[fallthrough]];
-    case 4: PHZ_LB_STEP(8); [[fallthrough]];
-    case 3: PHZ_LB_STEP(4); [[fallthrough]];
-    case 2: PHZ_LB_STEP(2); [[fallthrough]];
-    case 1: PHZ_LB_STEP(1); [[fallthrough]];
-    case 0: break;
-    }
-#undef PHZ_LB_STEP
-    base += (w[base] < key) ? 1 : 0;
-    return base;
+// s_vpos is padded with INT_MAX up to 2^wdepth entries; a negative key (the bracket's "no record" sentinel, a wrapped position) yields 0
+__device__ __forceinline__ int lds_lower_bound(const int32_t *w, int wdepth, int key) {
+    return wdepth == WIN_DSMALL ? window_lower_bound<WIN_DSMALL>(w, key) : window_lower_bound<WIN_DMAX>(w, key);
 }
 
 __device__ bool walk_lean(const int32_t *s_vpos, int wlen, int wdepth, int w0, const uint32_t *s_cig, uint32_t c_begin, uint32_t cig_cap,
@@ -370,7 +365,7 @@ __device__ bool walk_lean(const int32_t *s_vpos, int wlen, int wdepth, int w0, c
         const uint32_t w = s_cig[k - c_begin];
         const int len = (int)(w >> 4); const uint32_t op = w & 15, bit = 1u << op;
         const bool mlike = (bit & 0x181u) != 0;
-        if (__builtin_amdgcn_ballot_w64(op == OP_I) != 0) {
+        if (__builtin_amdgcn_uicmp(op, OP_I, 32 /* ICMP_EQ */) != 0) {          // the lane mask straight from the compare
             if (op == OP_I) {
                 bad |= (prev & 0x272u) != 0 || prev_len == 0 || nins == 2;      // after I / S / H / P / G / an empty op; a third insertion
                 nins++;
@@ -408,8 +403,10 @@ __device__ bool walk_lean(const int32_t *s_vpos, int wlen, int wdepth, int w0, c
                 i++;
             }
         }
-        g += (bit & 0x38Du) ? len : 0;
-        r += (bit & 0x193u) ? (uint32_t)len : 0u;
+        // (a mask of all ones from bit `op` of a table, by one signed bit-field extract: no compare into VCC and no hazard wait before a select;
+        // written as plain arithmetic the compiler folds it back into that pair)
+        g += len & __builtin_amdgcn_sbfe(0x38D, op, 1u);                          // M D N = X G advance the reference
+        r += (uint32_t)(len & __builtin_amdgcn_sbfe(0x193, op, 1u));              // M I S = X advance the read
         if (op == OP_N) { seg_start = g; t0 = -1; t1 = -1; }
         prev = bit; prev_len = (uint32_t)len;
     }
@@ -584,8 +581,8 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     if (tid == 0) { s_coff[TILE] = coff_end; s_ncand = 0; s_ncx = 0; s_nlong = 0; s_nins = 0; }
     if (tid < TILE / 32) s_poison[tid] = 0;
     const int wdepth = window_depth(vw.wlen);
-    // INT_MAX beyond the window: lds_lower_bound probes without a bounds test.  Its halving chain enters at step 2^(wdepth-1) and its closing
-    // probe reads at most index 2^wdepth - 1 -- but the scans of phase 1a read up to wlen -- so the padding stops at max(wlen, 2^wdepth)
+    // INT_MAX beyond the window: the search probes without a bounds test, up to index 2^wdepth - 1 (the depth class of the tile) -- and the scans of
+    // phase 1a read up to wlen -- so the padding stops at max(wlen, 2^wdepth)
 #ifdef PHZ_FILL_ALL
     const int wfill = MAP_WIN;
 #else

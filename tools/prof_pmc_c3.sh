@@ -7,7 +7,9 @@ R=$PWD; OUT=$R/gpurun_out/$1/pmc_kmap_c3; mkdir -p $OUT
 export TMPDIR=/tmp; cd /tmp
 run() { name=$1; shift
   rm -rf /tmp/pmc_$name
-  timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_$name -o p -- python $R/bench.py --full --no-cpu --no-phasing --no-c2 --no-bam --steps 3 --warmup 1 > /tmp/pmc_$name.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_$name -o p -- python $R/bench.py --full --no-cpu --no-phasing --no-c2 --no-bam --steps 3 --warmup 1 > /tmp/pmc_$name.log 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "pass $name ended with status $rc: no further pass is started"; tail -5 /tmp/pmc_$name.log; exit $rc; fi      # a pass that failed or hung: nothing more on this GPU
   f=$(find /tmp/pmc_$name -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then head -1 $f > $OUT/$name.csv; grep "k_map\|k_compact\|k_tile_window" $f >> $OUT/$name.csv; else echo "no counter file for $name"; tail -5 /tmp/pmc_$name.log; fi
 }
