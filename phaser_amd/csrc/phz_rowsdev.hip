@@ -22,6 +22,7 @@
 
 #include <type_traits>
 #include "phz_internal.h"
+#include "phz_scan.h"
 #include "phz_sort.h"
 #include "phz_text.h"
 #include "phz_uf.h"
@@ -2784,6 +2785,57 @@ extern "C" int phz_selftest_sort(phz_ctx *ctx, int key_bytes, const void *keys, 
     if (e == hipSuccess) e = hipMemcpyAsync(vals_out, where ? d[3].p : d[2].p, vb, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     return fin(e == hipSuccess ? PHZ_OK : phz_fail(ctx, PHZ_E_HIP, "phz_selftest_sort", e));
+}
+
+// Self-test entry of the device exclusive scans: scan_excl of phz_scan.h (impl 0), gscan_excl of phz_sort.h as its own dispatch chooses between the one-launch
+// look-back and the three-launch passes (impl 1), gscan_excl on the three-launch passes whatever the size (impl 2).  The n host values of in_bytes each are
+// staged in_skew elements behind an aligned device address, the result is written out_skew elements behind one (in_place: into the input buffer, one skew for
+// both), so that the 16-byte accesses of gs_load_rows / gs_store_rows are seen with their alignment gate closed as well as open.  out receives n + 2 values of
+// out_bytes: the n + 1 sums and the element BEHIND the total, which the entry fills with 0xA5 bytes before the scan and no scan may touch.  epoch_preset >= 0:
+// the ctx's status words are reserved for this scan first and ctx->scan_epoch is set (a fresh ctx only, and only above every epoch it has used), which is
+// how the tests reach the epoch reset.  Used by tests/test_scan.py (GPU and emulation) against a host cumulative sum; no reference counterpart.
+extern "C" int phz_selftest_scan(phz_ctx *ctx, int impl, int in_bytes, int out_bytes, int transform, const void *in, int64_t n, int in_skew, int out_skew, int in_place,
+                                 int64_t epoch_preset, void *out) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || impl < 0 || impl > 2 || (in_bytes != 4 && in_bytes != 8) || (out_bytes != 4 && out_bytes != 8) || out_bytes < in_bytes || n < 0 || n >= (1ll << 31) ||
+        (n && !in) || !out || in_skew < 0 || in_skew > 3 || out_skew < 0 || out_skew > 3 || (transform != 0 && transform != 1) || epoch_preset < -1 ||
+        epoch_preset >= (1ll << 30))
+        return PHZ_E_ARG;
+    if (impl == 0 && (in_bytes != 4 || out_bytes != 4 || transform)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: scan_excl is a scan of 32-bit values without a transform");
+    if (transform && (in_bytes != 4 || out_bytes != 4)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: the LabelWidth transform is instantiated for 32-bit values only");
+    if (in_place && (in_bytes != out_bytes || in_skew != out_skew)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: in place needs one element width and one skew");
+    PHZ_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t sm = ctx->stream;
+    DevBuf d[3];          // input, output, the scan's temporary
+    auto fin = [&](int code) { for (DevBuf &b : d) if (b.p) (void)hipFree(b.p); return code; };
+    int st = PHZ_OK;
+    const size_t ib = (size_t)in_bytes, ob = (size_t)out_bytes;
+    const size_t in_len = ((size_t)in_skew + (size_t)n + (in_place ? 2 : 0)) * ib, out_len = ((size_t)out_skew + (size_t)n + 2) * ob;
+    if ((st = phz_reserve(ctx, d[0], in_len + 16)) || (!in_place && (st = phz_reserve(ctx, d[1], out_len)))) return fin(st);
+    char *d_in = (char *)d[0].p + (size_t)in_skew * ib, *d_out = in_place ? d_in : (char *)d[1].p + (size_t)out_skew * ob;
+    hipError_t e = hipMemsetAsync(in_place ? d[0].p : d[1].p, 0xA5, in_place ? in_len : out_len, sm);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_in, in, (size_t)n * ib, hipMemcpyHostToDevice, sm);
+    if (e != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_selftest_scan: staging", e));
+    if (epoch_preset >= 0) {
+        const size_t before = ctx->scan_state.cap;
+        if ((st = phz_reserve(ctx, ctx->scan_state, 64 + (size_t)((n + GS_CHUNK - 1) / GS_CHUNK) * 8))) return fin(st);          // what gscan_excl asks for: it finds the words in place
+        if (ctx->scan_state.cap != before) {
+            if ((e = hipMemsetAsync(ctx->scan_state.p, 0, ctx->scan_state.cap, sm)) != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_selftest_scan: status words", e));
+            ctx->scan_ticket_base = 0;
+        }
+        ctx->scan_epoch = (uint32_t)epoch_preset;
+    }
+    typedef unsigned long long u64;
+    const bool force = impl == 2;
+    if (impl == 0) st = scan_excl(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2]);
+    else if (transform) st = gscan_excl<uint32_t, uint32_t, LabelWidth>(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2], force);
+    else if (out_bytes == 4) st = gscan_excl<uint32_t, uint32_t>(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2], force);
+    else if (in_bytes == 4) st = gscan_excl<uint32_t, u64>(ctx, (const uint32_t *)d_in, (u64 *)d_out, n, d[2], force);
+    else st = gscan_excl<u64, u64>(ctx, (const u64 *)d_in, (u64 *)d_out, n, d[2], force);
+    if (st != PHZ_OK) return fin(st);
+    e = hipMemcpyAsync(out, d_out, ((size_t)n + 2) * ob, hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipStreamSynchronize(sm);
+    return fin(e == hipSuccess ? PHZ_OK : phz_fail(ctx, PHZ_E_HIP, "phz_selftest_scan", e));
 }
 
 // SURVEY.md 8(b) `phz_hap_counts`: the number of DISTINCT reads (QNAMEs) in every (variant, allele, BAM) read list of the resident tally --

@@ -1,5 +1,6 @@
 // Device-wide exclusive scan of uint32 counts (hand-written; three passes: chunk sums, one-block scan of the sums, chunk-local scan
 // + base).  Header-only so that every translation unit that needs it gets its own copy of the kernels.
+// Tested directly by tests/test_scan.py (phz_selftest_scan with impl 0, against a host cumulative sum; emulation and GPU).
 #pragma once
 #include "phz_internal.h"
 

@@ -4,6 +4,9 @@
 // Radix sort: 8 bits per pass over the significant bits only.  One wave per tile of 1024 keys (16 rows of 64): the stable rank of a
 // key inside its row comes from eight wave ballots (lanes holding the same digit), the running per-digit offsets of the tile live
 // in LDS, so a pass is three launches: per-tile digit histograms, one scan over the [digit][tile] table, scatter.
+//
+// Tested directly: the scan by tests/test_scan.py (phz_selftest_scan, against a host cumulative sum; emulation and GPU), the sorts by tests/test_emu_sort.py and
+// tests/test_gpu_pipeline.py::test_device_sort_matches_a_stable_host_sort (phz_selftest_sort).
 #pragma once
 #include "phz_internal.h"
 
@@ -172,13 +175,14 @@ template <class TI, class F = GsIdentity> __global__ __launch_bounds__(256) void
     gs_store_rows<uint32_t>(out, n, chunk0, tid, v, base, s_prefix);
 }
 
-template <class TI, class TO, class F = GsIdentity> int gscan_excl(phz_ctx *ctx, const TI *in, TO *out /* [n + 1] */, int64_t n, DevBuf &tmp) {
+// force_three_launch: the three-launch passes also where the one-launch scan would be taken (the tests run both; no product caller sets it)
+template <class TI, class TO, class F = GsIdentity> int gscan_excl(phz_ctx *ctx, const TI *in, TO *out /* [n + 1] */, int64_t n, DevBuf &tmp, bool force_three_launch = false) {
     hipStream_t sm = ctx->stream;
     if (n <= 0) { PHZ_HIP(ctx, hipMemsetAsync(out, 0, sizeof(TO), sm)); return PHZ_OK; }
     const int64_t nb = (n + GS_CHUNK - 1) / GS_CHUNK;
     // (beyond a few million elements the prefix front of the look-back -- 64 tiles per round trip -- is slower than two streaming passes:
     //  18.8 M elements took 161 us in one launch)
-    if (sizeof(TO) == 4 && n < (int64_t)(4 << 20)) {
+    if (sizeof(TO) == 4 && n < (int64_t)(4 << 20) && !force_three_launch) {
       if constexpr (sizeof(TO) == 4) {
         const size_t before = ctx->scan_state.cap;
         if (int s = phz_reserve(ctx, ctx->scan_state, 64 + (size_t)nb * 8)) return s;
