@@ -49,9 +49,7 @@ int phz_ctx_destroy(phz_ctx *c) {
     if (!c) return PHZ_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    DevBuf *all[] = {&c->desc, &c->tile_w0, &c->scalars, &c->r_pos, &c->r_coff, &c->r_cig, &c->r_soff, &c->r_seq,
-                     &c->r_qual, &c->v_pos, &c->v_reflen, &c->c_read, &c->c_var, &c->c_code, &c->c_aux0, &c->c_aux1};
-    for (DevBuf *b : all) free_buf(*b);
+    free_buf(c->scalars); free_buf(c->map.desc); free_buf(c->map.tile_w0); free_buf(c->map.tab);
     for (DevBuf &b : c->scratch) free_buf(b);
     for (DevBuf &b : c->stage_pool) free_buf(b);
     for (DevBuf &b : c->tally_buf) free_buf(b);
@@ -63,9 +61,10 @@ int phz_ctx_destroy(phz_ctx *c) {
     if (c->mail_host.p) (void)hipHostFree(c->mail_host.p);
     free_buf(c->mail_dev);
     if (c->h_shard_tab.p) (void)hipHostFree(c->h_shard_tab.p);
+    if (c->map.tab_host.p) (void)hipHostFree(c->map.tab_host.p);
     if (c->h_bam_stage.p) (void)hipHostFree(c->h_bam_stage.p);
-    free_buf(c->shard_tab); free_buf(c->map_tab); free_buf(c->bam_comp); free_buf(c->bam_stream); free_buf(c->bam_work);
-    for (hipEvent_t e : c->map_ev) if (e) (void)hipEventDestroy(e);
+    free_buf(c->shard_tab); free_buf(c->bam_comp); free_buf(c->bam_stream); free_buf(c->bam_work);
+    for (hipEvent_t e : c->map.ev) if (e) (void)hipEventDestroy(e);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
     if (c->tab_ev) (void)hipEventDestroy(c->tab_ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);

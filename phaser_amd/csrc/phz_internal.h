@@ -55,21 +55,17 @@ struct phz_ctx {
     int64_t launches[PHZ_T_COUNT] = {0};
     int64_t counters[PHZ_C_COUNT] = {0};     // work counters accumulated by phz_tally (phz_get_counter)
     // scratch
-    DevBuf desc, tile_w0, scalars;
-    DevBuf h_scalars;                  // pinned host mirror of `scalars` (hipHostMalloc)
+    DevBuf scalars;
+    DevBuf h_scalars;                  // pinned host mirror of `scalars` (hipHostMalloc); its users (phz_as_histogram_sparse, K_map) wait for the stream before they return: no copy is ever pending on it
     DevBuf h_bam_stage;                // page-locked staging of the device BAM path (phz_bamdev.hip)
     DevBuf bam_comp, bam_stream, bam_work;       // the device BAM path's big buffers (compressed members, inflated stream, kept-record list) kept between BAMs: a fresh hipMalloc of ~19 GB
                                        // took 1.1-1.5 s every few calls (profiles/r05/cli_4bam_full.txt); given back to the runtime when an allocation fails
                                        // and by phz_ctx_destroy; PHZ_BAM_KEEP_BUFFERS=0 turns the cache off
     DevBuf mail_dev, mail_host;        // PhzMail: gathered small read-backs (device block, page-locked host image)
-    DevBuf shard_tab, h_shard_tab;     // shard table of a batched stage (device / pinned host image)
-    hipEvent_t tab_ev = nullptr; bool tab_pending = false;      // the last upload of the pinned image: the next one waits for it before it overwrites the image (a stage that returns without a host wait -- phz_as_cutoff_enqueue -- leaves its copy queued)
-    DevBuf map_tab;                    // K_map's own device copy of its shard table (shard_tab is shared with the tally / BAM stages)
-    std::vector<char> map_tab_image; void *map_tab_dev = nullptr;      // the image last uploaded to map_tab (a repeated submission skips the copy)
-    std::vector<hipEvent_t> map_ev;    // event pairs around every k_map launch of a batch
-    // staging for PHZ_HOST callers
-    DevBuf r_pos, r_coff, r_cig, r_soff, r_seq, r_qual, v_pos, v_reflen;
-    DevBuf c_read, c_var, c_code, c_aux0, c_aux1;
+    // shard table of a batched stage (device / pinned host image) and the last upload of the image: written and read by upload_tab (phz_tally.hip) ALONE, which waits for
+    // tab_ev before it overwrites or reallocates the image (a stage that returns without a host wait -- phz_as_cutoff_enqueue -- leaves its copy queued)
+    DevBuf shard_tab, h_shard_tab;
+    hipEvent_t tab_ev = nullptr; bool tab_pending = false;
     // generic per-call scratch slots (PhzScratch), grown on demand and reused across calls
     DevBuf scratch[SC_COUNT];
     // device copies of PHZ_HOST callers' arrays (Staging): slot k of a call reuses stage_pool[k], grown on demand, so the
@@ -96,10 +92,18 @@ struct phz_ctx {
         uint32_t *rl_start = nullptr, *rl_list = nullptr;
         uint8_t *linked = nullptr, *line_cls = nullptr;
     } tally;
-    int map_tile_reads = 0;
-    int map_slot_cap = 0;      // calls per tile slot of K_map's staging area
-    int64_t map_ovf_cap = 0;   // calls the overflow area behind the slots holds (grown to what the densest submission needed)
-    long long map_ovf_image[5] = {0, 0, 0, 0, 0};      // the overflow-area record last uploaded (+ where): a repeated submission skips the copy
+    // what K_map keeps between submissions (phz_map.hip alone reads and writes it; the layouts of tab and desc: MapTab, MapDesc there)
+    struct {
+        DevBuf tab;                    // device: shard table, per-shard call bases, overflow-area record
+        DevBuf tab_host;               // pinned image of `tab`.  K_map waits for its stream before it returns, so no copy out of it is ever pending: no event
+        std::vector<char> tab_image; void *tab_dev = nullptr;      // the table last uploaded to tab (a repeated submission skips the copy)
+        long long ovf_image[5] = {0, 0, 0, 0, 0};      // the overflow-area record last uploaded (+ where): likewise
+        hipEvent_t ev[2] = {nullptr, nullptr};         // around the k_map launch of an attempt
+        DevBuf tile_w0, desc;          // per-tile window words; tile prefix + chunk sums of the two-level scan
+        int tile_reads = 0;
+        int slot_cap = 0;              // calls per tile slot of the staging area
+        int64_t ovf_cap = 0;           // calls the overflow area behind the slots holds (grown to what the densest submission needed)
+    } map;
 };
 
 // Small values a stage reads back before it can go on (counts, sizes, flags: a few words each, scattered over device buffers) travel as ONE block:

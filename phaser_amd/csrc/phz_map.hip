@@ -1044,184 +1044,251 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs c) {
     else compact_run<false>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], T0, M, lane, si0);
 }
 
+// ---- layouts of the buffers the driver carves into parts: byte offsets computed once, typed pointers handed out for a device buffer or its pinned image
+template <class T> static T *part_at(const DevBuf &b, size_t off) { return (T *)((char *)b.p + off); }
+
+// ctx->map.tab and its image ctx->map.tab_host: [ShardDev x m][tile0 x (m+1)][shard_base x m][OvfArea].  [0, table_bytes) is the shard table a repeated
+// submission does not upload again; shard_base exists on the device only (k_shard_totals recomputes it in every attempt)
+struct MapTab {
+    size_t off_tile0, off_base, off_ovf;
+    explicit MapTab(int m) : off_tile0((size_t)m * sizeof(ShardDev)), off_base(off_tile0 + (size_t)(m + 1) * 8), off_ovf(off_base + (size_t)m * 8) {}
+    size_t table_bytes() const { return off_base; }
+    size_t bytes() const { return off_ovf + 64; }
+    ShardDev *shards(const DevBuf &b) const { return part_at<ShardDev>(b, 0); }
+    OvfArea *ovf(const DevBuf &b) const { return part_at<OvfArea>(b, off_ovf); }
+    int64_t *tile0(const DevBuf &b) const { return part_at<int64_t>(b, off_tile0); }
+    int64_t *shard_base(const DevBuf &b) const { return part_at<int64_t>(b, off_base); }
+};
+// ctx->map.desc: [tile_pref x ntiles][chunk_sum x nchunks][chunk_base x nchunks][chunk_max x nchunks]
+struct MapDesc {
+    size_t off_sum, off_base, off_max, bytes;
+    MapDesc(int64_t ntiles, int nchunks) : off_sum(((size_t)ntiles * 4 + 15) & ~(size_t)15), off_base(off_sum + (size_t)nchunks * 8), off_max(off_base + (size_t)nchunks * 8),
+                                           bytes((size_t)ntiles * 4 + (size_t)nchunks * 24 + 64) {}
+    int32_t *tile_pref(const DevBuf &b) const { return part_at<int32_t>(b, 0); }
+    int64_t *chunk_sum(const DevBuf &b) const { return part_at<int64_t>(b, off_sum); }
+    int64_t *chunk_base(const DevBuf &b) const { return part_at<int64_t>(b, off_base); }
+    int32_t *chunk_max(const DevBuf &b) const { return part_at<int32_t>(b, off_max); }
+};
+// ctx->scalars and its pinned mirror ctx->h_scalars, 8-byte words: [0] calls of the batch, [1] densest tile, [2, 2 + m) calls per shard, [2 + m] overflow-area cursor
+struct MapScalars {
+    int m;
+    size_t readback_bytes() const { return (size_t)8 * (m + 3); }
+    size_t bytes() const { return readback_bytes() + 128; }
+    unsigned long long *words(const DevBuf &b) const { return part_at<unsigned long long>(b, 0); }
+    unsigned long long &shard_calls(const DevBuf &b, int k) const { return words(b)[2 + k]; }
+    unsigned long long *cursor(const DevBuf &b) const { return words(b) + 2 + m; }
+};
+
+// the PHZ_MAP_* switches of one submission (read per call: tests change them between calls on one ctx)
+struct MapKnobs {
+    int blk, rpt, dbg; unsigned dyn_lds; bool two_planes;
+    static int positive(const char *name, int dflt) { const char *e = getenv(name); return e && atoi(e) > 0 ? atoi(e) : dflt; }
+    // (PHZ_MAP_DYNLDS, an experiment: bytes of dynamic LDS nobody uses, to bound the workgroups per CU)
+    MapKnobs() : blk(positive("PHZ_MAP_BLOCK", 128)), rpt(positive("PHZ_MAP_RPT", 2)), dyn_lds((unsigned)positive("PHZ_MAP_DYNLDS", 0)), two_planes(getenv("PHZ_MAP_TWO_PLANES") != nullptr) {
+        const char *e = getenv("PHZ_MAP_DBG"); dbg = e ? atoi(e) : 0;
+    }
+};
+
+// What one submission knows.  Its functions are the sections of launch_map_batch in stream order; the one host wait of an attempt is the end of attempt().
+struct MapSubmission {
+    phz_ctx *ctx; hipStream_t sm; DevBuf *S;
+    const int n; const phz_reads *r; const phz_variants *v; const int baseq; const phz_calls *out; int64_t *n_calls;
+    const MapKnobs knobs; int tile_reads = 0;
+    std::vector<int> live; std::vector<int64_t> tile0;          // live shards (records and variants present); first tile of each, then the tile count
+    int m = 0, nchunks = 0; int64_t ntiles = 0; bool one_plane = false;
+    MapTab tab{0}; MapDesc desc{0, 0}; MapScalars scal{0};
+    float ms_total = 0;
+
+    MapSubmission(phz_ctx *c, int n_, const phz_reads *r_, const phz_variants *v_, int baseq_, const phz_calls *out_, int64_t *n_calls_)
+        : ctx(c), sm(c->stream), S(c->scratch), n(n_), r(r_), v(v_), baseq(baseq_), out(out_), n_calls(n_calls_) {}
+    template <class T> T *scr(int slot) const { return (T *)S[slot].p; }
+
+    // ---- the live shards and their tile ranges; the limits of the tile word (13 bits of shard, 31 of tile)
+    int live_shards_and_tiles() {
+        // (64 x 2 / 64 x 4 / 128 x 4 / 256 x 4 records per tile were swept in rounds 1-3 -- 1.84 ms and worse against 1.28 -- and are no longer built:
+        // their tiles cannot be held at eight waves per SIMD)
+        if (!((knobs.blk == 128 || knobs.blk == 256) && knobs.rpt == 2)) return phz_fail(ctx, PHZ_E_ARG, "bad PHZ_MAP_BLOCK / PHZ_MAP_RPT");
+        tile_reads = knobs.blk * knobs.rpt;
+        for (int i = 0; i < n; i++) {
+            if (v[i].n > 0x7fffffff) return phz_fail(ctx, PHZ_E_ARG, "too many variants in one shard");
+            if (r[i].n_reads > 0 && v[i].n > 0) { live.push_back(i); tile0.push_back(ntiles); ntiles += (r[i].n_reads + tile_reads - 1) / tile_reads; }
+        }
+        tile0.push_back(ntiles);
+        m = (int)live.size();
+        if (ntiles >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "too many tiles in one submission");
+        if (m > 0x1FFF) return phz_fail(ctx, PHZ_E_ARG, "more than 8191 shards in one submission");
+        nchunks = (int)((ntiles + 1023) / 1024);
+        tab = MapTab(m); desc = MapDesc(ntiles, nchunks); scal = MapScalars{m};
+        return PHZ_OK;
+    }
+    // ---- the shard table built in K_map's pinned image and uploaded unless the device holds these very bytes (same shards, same output buffers)
+    int shard_table() {
+        auto &M = ctx->map;
+        if (int s = phz_reserve_host(ctx, M.tab_host, tab.bytes())) return s;
+        if (int s = phz_reserve(ctx, M.tab, tab.bytes())) return s;
+        ShardDev *hs = tab.shards(M.tab_host);
+        // every shard of the submission carries the one-byte plane (a caller's choice: phz_reads.bq; PHZ_MAP_ONE_PLANE=1 for the Python host): the ONE instantiation
+        // reads it (PHZ_MAP_TWO_PLANES=1: the two-plane instantiation regardless).  Same-box A/B of the two production instantiations on the whole-genome sample:
+        // 1.0940 against 1.0928 ms -- the plane buys nothing there, so nothing in the product builds it by default
+        one_plane = !knobs.two_planes;
+        for (int k = 0; k < m; k++) {
+            const int i = live[(size_t)k];
+            ShardDev &d = hs[k];
+            d.pos = r[i].pos; d.cigar_off = r[i].cigar_off; d.cigar = r[i].cigar; d.seq_off = r[i].seq_off; d.seq2 = r[i].seq2; d.qual = r[i].qual; d.bq = r[i].bq;
+            d.n = r[i].n_reads; d.vpos = v[i].pos; d.nv = (int)v[i].n; d.pad = 0;
+            d.o_read = out[i].read_idx; d.o_var = out[i].var_idx; d.o_code = out[i].code; d.o_aux0 = out[i].aux0; d.o_aux1 = out[i].aux1;
+            if (!d.o_aux0 || !d.o_aux1) { d.o_aux0 = nullptr; d.o_aux1 = nullptr; }           // both or none
+            d.cap = out[i].cap;
+            if (!d.bq) one_plane = false;
+        }
+        memcpy(tab.tile0(M.tab_host), tile0.data(), (size_t)(m + 1) * 8);
+        const char *img = (const char *)hs;
+        if (M.tab_image.size() != tab.table_bytes() || M.tab_dev != M.tab.p || memcmp(M.tab_image.data(), img, tab.table_bytes()) != 0) {
+            PHZ_HIP(ctx, hipMemcpyAsync(M.tab.p, img, tab.table_bytes(), hipMemcpyHostToDevice, sm));
+            M.tab_image.assign(img, img + tab.table_bytes());
+            M.tab_dev = M.tab.p;
+        }
+        for (hipEvent_t &e : M.ev) if (!e) PHZ_HIP(ctx, hipEventCreate(&e));
+        return PHZ_OK;
+    }
+    // ---- every buffer whose size the tile count decides; the slot size of the staging area, fixed at the ctx's first submission
+    // Staging: every tile owns a slot of slot_cap calls (half a tile's records: the typical RNA-seq tile has ~60) and a tile with more takes a stretch of
+    // the OVERFLOW AREA behind the slots (one cursor step per such tile).  The area starts at a quarter of the slots' size and is kept at what the densest
+    // submission so far needed; a submission that needs more is redone once with exactly that (round 4 sized EVERY slot for the densest tile: 50 GB for a
+    // deep sample with one dense region).  PHZ_MAP_SLOT_CAP: another slot size (tests: 8, so that most tiles overflow).
+    int reserve() {
+        auto &M = ctx->map;
+        if (int s = reserve_all(ctx, {{M.tile_w0, (size_t)ntiles * 16}, {S[SC_MAP_TILE_TOTAL], (size_t)ntiles * 4}, {M.desc, desc.bytes}, {ctx->scalars, scal.bytes()}})) return s;
+        if (int s = phz_reserve_host(ctx, ctx->h_scalars, scal.bytes())) return s;
+        if (int s = phz_reserve(ctx, S[SC_MAP_TILE_OVF], (size_t)ntiles * 4)) return s;
+        if (M.slot_cap <= 0 || M.tile_reads != tile_reads) {
+            M.slot_cap = tile_reads / 2 < 64 ? 64 : tile_reads / 2; M.tile_reads = tile_reads;
+            const char *e = getenv("PHZ_MAP_SLOT_CAP"); if (e && atoi(e) >= 1) M.slot_cap = atoi(e);
+        }
+        return PHZ_OK;
+    }
+    // ---- the staging area at the overflow area's current size: bt's view of it, and the OvfArea record on the device (in K_map's own buffer: ctx->scalars is
+    // shared scratch), uploaded only when it changed -- like the shard table --; the cursor is zeroed by the pre-pass kernel: no extra operation on the stream per step
+    int staging_area(MapBatch &bt) {
+        auto &M = ctx->map;
+        const size_t base_slots = (size_t)ntiles * (size_t)M.slot_cap;
+        if (M.ovf_cap < (int64_t)(base_slots / 4)) M.ovf_cap = (int64_t)(base_slots / 4);
+        if (M.ovf_cap < 65536) M.ovf_cap = 65536;
+        const size_t slots = base_slots + (size_t)M.ovf_cap;
+        if (slots >= 0xFFFFFFF0ull) return phz_fail(ctx, PHZ_E_ARG, "K_map staging area beyond 2^32 slots: submit the shards in smaller batches");
+        if (int s = phz_reserve(ctx, S[SC_MAP_STAGE], slots * 16)) return s;
+        bt.stage = scr<uint2>(SC_MAP_STAGE); bt.side = (uint32_t *)(bt.stage + slots); bt.slots = (int64_t)slots;          // [packed record x slots][side word x 2 slots]
+        bt.slot_cap = M.slot_cap;
+        OvfArea *h_ov = tab.ovf(M.tab_host), *d_ov = tab.ovf(M.tab);
+        h_ov->tile_first = scr<uint32_t>(SC_MAP_TILE_OVF); h_ov->cursor = scal.cursor(ctx->scalars); h_ov->base = (long long)base_slots; h_ov->cap = (long long)M.ovf_cap;
+        const long long img[5] = {(long long)(intptr_t)h_ov->tile_first, (long long)(intptr_t)h_ov->cursor, h_ov->base, h_ov->cap, (long long)(intptr_t)d_ov};
+        if (memcmp(img, M.ovf_image, sizeof img) != 0) {
+            PHZ_HIP(ctx, hipMemcpyAsync(d_ov, h_ov, sizeof(OvfArea), hipMemcpyHostToDevice, sm));
+            memcpy(M.ovf_image, img, sizeof img);
+        }
+        bt.ovf = d_ov;
+        return PHZ_OK;
+    }
+    template <int B, int R> void launch_k_map(const MapBatch &bt) const {
+        const dim3 grid((unsigned)ntiles), block(B);
+        if (bt.dbg) hipLaunchKernelGGL((k_map<B, R, true>), grid, block, knobs.dyn_lds, sm, bt);
+        else if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true>), grid, block, knobs.dyn_lds, sm, bt);
+        else hipLaunchKernelGGL((k_map<B, R, false>), grid, block, knobs.dyn_lds, sm, bt);
+    }
+    // ---- one attempt: pre-pass, k_map between its two events, the scan of the tile totals, per-shard totals, compaction, the words read back.  WAIT
+    int attempt() {
+        auto &M = ctx->map;
+        MapBatch bt;
+        bt.shards = tab.shards(M.tab); bt.tile0 = tab.tile0(M.tab); bt.n_shards = m; bt.baseq = baseq;
+        bt.tile_w0 = (int32_t *)M.tile_w0.p; bt.tile_total = scr<int32_t>(SC_MAP_TILE_TOTAL); bt.ntiles = ntiles;
+        if (int s = staging_area(bt)) return s;
+        bt.dbg = knobs.dbg; bt.prof = nullptr;
+        if (bt.dbg & 2048) { if (int s = phz_reserve(ctx, S[SC_MAP_PROFILE], (size_t)ntiles * 64)) return s; bt.prof = scr<unsigned long long>(SC_MAP_PROFILE); }
+        hipLaunchKernelGGL(k_tile_window, dim3(nblk(ntiles)), dim3(256), 0, sm, bt, tile_reads);
+        PHZ_HIP(ctx, hipEventRecord(M.ev[0], sm));
+        if (knobs.blk == 128) launch_k_map<128, 2>(bt); else launch_k_map<256, 2>(bt);
+        PHZ_HIP(ctx, hipEventRecord(M.ev[1], sm));
+        int32_t *tile_pref = desc.tile_pref(M.desc); int64_t *chunk_sum = desc.chunk_sum(M.desc), *chunk_base = desc.chunk_base(M.desc); int32_t *chunk_max = desc.chunk_max(M.desc);
+        unsigned long long *d_words = scal.words(ctx->scalars);
+        hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)nchunks), dim3(1024), 0, sm, (const int32_t *)bt.tile_total, ntiles, tile_pref, chunk_sum, chunk_max);
+        hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(1024), 0, sm, (const int64_t *)chunk_sum, (const int32_t *)chunk_max, nchunks, chunk_base, d_words);
+        hipLaunchKernelGGL(k_shard_totals, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, sm, bt.tile0, m, ntiles, (const int32_t *)tile_pref, (const int64_t *)chunk_base, d_words,
+                           tab.shard_base(M.tab));
+        CompactArgs c;
+        c.stage = bt.stage; c.side = bt.side; c.slots = bt.slots;
+        c.shards = bt.shards; c.tile0 = bt.tile0; c.n_shards = m;
+        c.tile_total = bt.tile_total; c.tile_pref = tile_pref; c.chunk_base = chunk_base; c.shard_base = tab.shard_base(M.tab);
+        c.tile_w0 = bt.tile_w0;
+        c.slot_cap = bt.slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = scr<const uint32_t>(SC_MAP_TILE_OVF);
+        hipLaunchKernelGGL(k_compact, dim3((unsigned)((ntiles + 4 * CT - 1) / (4 * CT))), dim3(256), 0, sm, c);
+        PHZ_HIP(ctx, hipGetLastError());
+        PHZ_HIP(ctx, hipMemcpyAsync(scal.words(ctx->h_scalars), d_words, scal.readback_bytes(), hipMemcpyDeviceToHost, sm));
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        float ms = 0;
+        PHZ_HIP(ctx, hipEventElapsedTime(&ms, M.ev[0], M.ev[1]));
+        if (bt.prof) if (int s = profile_report(bt.prof, ms)) return s;
+        ms_total += ms;
+        return PHZ_OK;
+    }
+    // ---- PHZ_MAP_DBG & 2048: mean time between the stamps of a tile (wall_clock64: 100 MHz), first wave's view
+    int profile_report(const unsigned long long *prof, float ms) {
+        std::vector<unsigned long long> pr((size_t)ntiles * 8);
+        PHZ_HIP(ctx, hipMemcpy(pr.data(), prof, pr.size() * 8, hipMemcpyDeviceToHost));
+        double seg[7] = {0, 0, 0, 0, 0, 0, 0}; double life = 0;
+        for (int64_t t = 0; t < ntiles; t++) { for (int k = 0; k < 7; k++) seg[k] += (double)(pr[8 * t + k + 1] - pr[8 * t + k]); life += (double)(pr[8 * t + 7] - pr[8 * t]); }
+        fprintf(stderr, "[k_map profile] %lld tiles, kernel %.3f ms, tile lifetime %.2f us: stage loads -> LDS %.2f | single-run records + first gathers %.2f | barrier %.2f | "
+                        "multi-op walk %.2f | candidate gathers + resolve %.2f | scan %.2f | flush %.2f us\n", (long long)ntiles, ms, life / ntiles / 100.0,
+                seg[0] / ntiles / 100.0, seg[1] / ntiles / 100.0, seg[2] / ntiles / 100.0, seg[3] / ntiles / 100.0, seg[4] / ntiles / 100.0, seg[5] / ntiles / 100.0, seg[6] / ntiles / 100.0);
+        return PHZ_OK;
+    }
+    // ---- the overflow area: did every dense tile of the last attempt find room; if not, sized for the calls of all dense tiles (+ slack for the next submission)
+    bool overflow_area_held() const { return (int64_t)*scal.cursor(ctx->h_scalars) <= ctx->map.ovf_cap; }
+    void grow_overflow_area() { const unsigned long long need = *scal.cursor(ctx->h_scalars); ctx->map.ovf_cap = (int64_t)need + (int64_t)(need / 16) + 4096; }
+    // ---- timing; calls per shard, PHZ_E_CAPACITY when a shard's buffers were too small for them (its first `cap` calls are in place)
+    int results() {
+        ctx->last_ms[PHZ_T_MAP] = ms_total; ctx->total_ms[PHZ_T_MAP] += ms_total; ctx->launches[PHZ_T_MAP]++;
+        int st = PHZ_OK;
+        for (int k = 0; k < m; k++) {
+            const int i = live[(size_t)k];
+            n_calls[i] = (int64_t)scal.shard_calls(ctx->h_scalars, k);
+            if (n_calls[i] > out[i].cap) st = PHZ_E_CAPACITY;
+        }
+        return st;
+    }
+};
+
 }  // namespace
 
 // All shards of a submission run through ONE grid per stage (pre-pass, k_map, tile scan, per-shard totals, compaction): a whole
 // genome is 5 launches and one host wait, with no per-shard ramp-up / tail.
 // (Tried and dropped, round 3: k_map writing every call to its final place, the calls before a tile found by decoupled look-back over
 // per-tile status words -- no staging, no k_compact.  A tile knows its count only at the END of its work (the count needs the quality
-// bytes), so its flush waits for every earlier tile still in flight: 3.01 ms against 1.32 + 0.16 ms for k_map + k_compact.)  A batch whose densest tile overflows its staging slot
-// is redone with larger slots (rare: the slot capacity is kept across calls).
-static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_variants *v, int baseq, const phz_calls *out, int64_t *n_calls);
+// bytes), so its flush waits for every earlier tile still in flight: 3.01 ms against 1.32 + 0.16 ms for k_map + k_compact.)  A batch whose densest tiles overflow
+// the staging area is redone with a larger overflow area (rare: its size is kept across calls).
+static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_variants *v, int baseq, const phz_calls *out, int64_t *n_calls) {
+    for (int i = 0; i < n; i++) n_calls[i] = 0;
+    if (n <= 0) return PHZ_OK;
+    MapSubmission sub(ctx, n, r, v, baseq, out, n_calls);
+    if (int s = sub.live_shards_and_tiles()) return s;
+    if (sub.m == 0) return PHZ_OK;
+    if (int s = sub.shard_table()) return s;
+    if (int s = sub.reserve()) return s;
+    for (int attempt = 0; ; attempt++) {
+        if (int s = sub.attempt()) return s;
+        if (sub.overflow_area_held()) break;
+        if (attempt == 2) return phz_fail(ctx, PHZ_E_HIP, "K_map staging overflow area did not converge");
+        sub.grow_overflow_area();
+    }
+    return sub.results();
+}
 
 int phz_launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_variants *v, int baseq, const phz_calls *out,
                          int64_t *n_calls) {
     const int s = launch_map_batch(ctx, n, r, v, baseq, out, n_calls);
-    // map_tab_image claims "these bytes are in ctx->map_tab" (nobody else writes map_tab; its [tab_bytes, +m*8) tail, shard_base, is recomputed by every
-    // launch).  A submission that failed anywhere between the upload and its stream wait may not have delivered them: forget the image.
-    if (s != PHZ_OK && s != PHZ_E_CAPACITY) { ctx->map_tab_image.clear(); ctx->map_tab_dev = nullptr; memset(ctx->map_ovf_image, 0, sizeof ctx->map_ovf_image); }
+    // map.tab_image and map.ovf_image claim "these bytes are in ctx->map.tab".  A submission that failed anywhere between an upload and its stream wait may not
+    // have delivered them: forget both.
+    if (s != PHZ_OK && s != PHZ_E_CAPACITY) { ctx->map.tab_image.clear(); ctx->map.tab_dev = nullptr; memset(ctx->map.ovf_image, 0, sizeof ctx->map.ovf_image); }
     return s;
-}
-
-static int launch_map_batch(phz_ctx *ctx, int n, const phz_reads *r, const phz_variants *v, int baseq, const phz_calls *out, int64_t *n_calls) {
-    for (int i = 0; i < n; i++) n_calls[i] = 0;
-    if (n <= 0) return PHZ_OK;
-    int rpt = 2, blk = 128;
-    { const char *e = getenv("PHZ_MAP_RPT"); if (e && atoi(e) > 0) rpt = atoi(e); }
-    { const char *e = getenv("PHZ_MAP_BLOCK"); if (e && atoi(e) > 0) blk = atoi(e); }
-    // (64 x 2 / 64 x 4 / 128 x 4 / 256 x 4 records per tile were swept in rounds 1-3 -- 1.84 ms and worse against 1.28 -- and are no longer built:
-    // their tiles cannot be held at eight waves per SIMD)
-    if (!((blk == 128 || blk == 256) && rpt == 2)) return phz_fail(ctx, PHZ_E_ARG, "bad PHZ_MAP_BLOCK / PHZ_MAP_RPT");
-    const int tile_reads = blk * rpt;
-    // live shards (records and variants present) and their tile ranges
-    std::vector<int> live;
-    for (int i = 0; i < n; i++) {
-        if (v[i].n > 0x7fffffff) return phz_fail(ctx, PHZ_E_ARG, "too many variants in one shard");
-        if (r[i].n_reads > 0 && v[i].n > 0) live.push_back(i);
-    }
-    const int m = (int)live.size();
-    if (m == 0) return PHZ_OK;
-    // host image of the shard table: [ShardDev x m][tile0 x (m+1)], pinned; device copy in ctx->map_tab
-    const size_t tab_bytes = (size_t)m * sizeof(ShardDev) + (size_t)(m + 1) * 8;
-    if (int s = phz_reserve_host(ctx, ctx->h_shard_tab, tab_bytes)) return s;
-    if (int s = phz_reserve(ctx, ctx->map_tab, tab_bytes + (size_t)m * 8 + 64)) return s;          // [table][shard_base x m][overflow-area record]
-    ShardDev *hs = (ShardDev *)ctx->h_shard_tab.p;
-    int64_t *ht0 = (int64_t *)((char *)ctx->h_shard_tab.p + (size_t)m * sizeof(ShardDev));
-    int64_t ntiles = 0;
-    for (int k = 0; k < m; k++) {
-        const int i = live[(size_t)k];
-        ShardDev &d = hs[k];
-        d.pos = r[i].pos; d.cigar_off = r[i].cigar_off; d.cigar = r[i].cigar; d.seq_off = r[i].seq_off; d.seq2 = r[i].seq2; d.qual = r[i].qual; d.bq = r[i].bq;
-        d.n = r[i].n_reads; d.vpos = v[i].pos; d.nv = (int)v[i].n; d.pad = 0;
-        d.o_read = out[i].read_idx; d.o_var = out[i].var_idx; d.o_code = out[i].code; d.o_aux0 = out[i].aux0; d.o_aux1 = out[i].aux1;
-        if (!d.o_aux0 || !d.o_aux1) { d.o_aux0 = nullptr; d.o_aux1 = nullptr; }           // both or none
-        d.cap = out[i].cap;
-        ht0[k] = ntiles;
-        ntiles += (r[i].n_reads + tile_reads - 1) / tile_reads;
-    }
-    ht0[m] = ntiles;
-    // every shard of the submission carries the one-byte plane (a caller's choice: phz_reads.bq; PHZ_MAP_ONE_PLANE=1 for the Python host): the ONE instantiation
-    // reads it (PHZ_MAP_TWO_PLANES=1: the two-plane instantiation regardless).  Same-box A/B of the two production instantiations on the whole-genome sample:
-    // 1.0940 against 1.0928 ms -- the plane buys nothing there, so nothing in the product builds it by default
-    bool one_plane = m > 0 && getenv("PHZ_MAP_TWO_PLANES") == nullptr;
-    for (int k = 0; k < m; k++) if (!hs[k].bq) one_plane = false;
-    if (ntiles >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "too many tiles in one submission");
-    if (m > 0x1FFF) return phz_fail(ctx, PHZ_E_ARG, "more than 8191 shards in one submission");
-    const ShardDev *d_shards = (const ShardDev *)ctx->map_tab.p;
-    const int64_t *d_tile0 = (const int64_t *)((char *)ctx->map_tab.p + (size_t)m * sizeof(ShardDev));
-    int64_t *d_shard_base = (int64_t *)((char *)ctx->map_tab.p + tab_bytes);
-    hipStream_t sm = ctx->stream;
-    // the table of a repeated submission (same shards, same output buffers) is already on the device
-    if (ctx->map_tab_image.size() != tab_bytes || ctx->map_tab_dev != ctx->map_tab.p || memcmp(ctx->map_tab_image.data(), ctx->h_shard_tab.p, tab_bytes) != 0) {
-        PHZ_HIP(ctx, hipMemcpyAsync(ctx->map_tab.p, ctx->h_shard_tab.p, tab_bytes, hipMemcpyHostToDevice, sm));
-        ctx->map_tab_image.assign((const char *)ctx->h_shard_tab.p, (const char *)ctx->h_shard_tab.p + tab_bytes);
-        ctx->map_tab_dev = ctx->map_tab.p;
-    }
-    if ((int)ctx->map_ev.size() < 2) {
-        ctx->map_ev.resize(2, nullptr);
-        for (auto &e : ctx->map_ev) if (!e) PHZ_HIP(ctx, hipEventCreate(&e));
-    }
-    DevBuf *S = ctx->scratch;
-    if (int s = phz_reserve(ctx, ctx->tile_w0, (size_t)ntiles * 16)) return s;
-    if (int s = phz_reserve(ctx, S[SC_MAP_TILE_TOTAL], (size_t)ntiles * 4)) return s;
-    const int nchunks = (int)((ntiles + 1023) / 1024);
-    if (int s = phz_reserve(ctx, ctx->desc, (size_t)ntiles * 4 + (size_t)nchunks * 24 + 64)) return s;
-    int32_t *tile_pref = (int32_t *)ctx->desc.p;
-    int64_t *chunk_sum = (int64_t *)((char *)ctx->desc.p + (((size_t)ntiles * 4 + 15) & ~(size_t)15));
-    int64_t *chunk_base = chunk_sum + nchunks;
-    int32_t *chunk_max = (int32_t *)(chunk_base + nchunks);
-    if (int s = phz_reserve(ctx, ctx->scalars, (size_t)8 * (m + 3) + 128)) return s;           // [0] total, [1] densest tile, [2, 2 + m) calls per shard, [2 + m] overflow-area cursor, then the OvfArea record
-    if (int s = phz_reserve_host(ctx, ctx->h_scalars, (size_t)8 * (m + 3) + 128)) return s;
-    if (int s = phz_reserve(ctx, S[SC_MAP_TILE_OVF], (size_t)ntiles * 4)) return s;                          // tile_ovf
-    unsigned long long *scal = (unsigned long long *)ctx->h_scalars.p;
-    // Staging: every tile owns a slot of slot_cap calls (half a tile's records: the typical RNA-seq tile has ~60) and a tile with more takes a stretch of
-    // the OVERFLOW AREA behind the slots (one cursor step per such tile).  The area starts at a quarter of the slots' size and is kept at what the densest
-    // submission so far needed; a submission that needs more is redone once with exactly that (round 4 sized EVERY slot for the densest tile: 50 GB for a
-    // deep sample with one dense region).  PHZ_MAP_SLOT_CAP: another slot size (tests: 8, so that most tiles overflow).
-    if (ctx->map_slot_cap <= 0 || ctx->map_tile_reads != tile_reads) {
-        ctx->map_slot_cap = tile_reads / 2 < 64 ? 64 : tile_reads / 2; ctx->map_tile_reads = tile_reads;
-        const char *e = getenv("PHZ_MAP_SLOT_CAP"); if (e && atoi(e) >= 1) ctx->map_slot_cap = atoi(e);
-    }
-    float ms_total = 0;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        const int slot_cap = ctx->map_slot_cap;
-        const size_t base_slots = (size_t)ntiles * (size_t)slot_cap;
-        if (ctx->map_ovf_cap < (int64_t)(base_slots / 4)) ctx->map_ovf_cap = (int64_t)(base_slots / 4);
-        if (ctx->map_ovf_cap < 65536) ctx->map_ovf_cap = 65536;
-        const size_t slots = base_slots + (size_t)ctx->map_ovf_cap;
-        if (slots >= 0xFFFFFFF0ull) return phz_fail(ctx, PHZ_E_ARG, "K_map staging area beyond 2^32 slots: submit the shards in smaller batches");
-        if (int s = phz_reserve(ctx, S[SC_MAP_STAGE], slots * 16)) return s;
-        MapBatch bt;
-        bt.shards = d_shards; bt.tile0 = d_tile0; bt.n_shards = m; bt.baseq = baseq;
-        bt.stage = (uint2 *)S[SC_MAP_STAGE].p; bt.side = (uint32_t *)((char *)S[SC_MAP_STAGE].p + slots * 8); bt.slots = (int64_t)slots;
-        bt.tile_w0 = (int32_t *)ctx->tile_w0.p; bt.tile_total = (int32_t *)S[SC_MAP_TILE_TOTAL].p;
-        bt.slot_cap = slot_cap; bt.ntiles = ntiles;
-        {
-            OvfArea *h_ov = (OvfArea *)((char *)ctx->h_scalars.p + (size_t)8 * (m + 3) + 64);          // (pinned; behind the words the read-back fills)
-            h_ov->tile_first = (uint32_t *)S[SC_MAP_TILE_OVF].p; h_ov->cursor = (unsigned long long *)ctx->scalars.p + (2 + m); h_ov->base = (long long)base_slots; h_ov->cap = (long long)ctx->map_ovf_cap;
-            OvfArea *d_ov = (OvfArea *)((char *)ctx->map_tab.p + tab_bytes + (size_t)m * 8);            // in K_map's own buffer: ctx->scalars is shared scratch
-            // (uploaded only when it changed -- like the shard table --; the cursor is zeroed by the pre-pass kernel: no extra operation on the stream per step)
-            long long img[5] = {(long long)(intptr_t)h_ov->tile_first, (long long)(intptr_t)h_ov->cursor, h_ov->base, h_ov->cap, (long long)(intptr_t)d_ov};
-            if (memcmp(img, ctx->map_ovf_image, sizeof img) != 0) {
-                PHZ_HIP(ctx, hipMemcpyAsync(d_ov, h_ov, sizeof(OvfArea), hipMemcpyHostToDevice, sm));
-                memcpy(ctx->map_ovf_image, img, sizeof img);
-            }
-            bt.ovf = d_ov;
-        }
-        { const char *e = getenv("PHZ_MAP_DBG"); bt.dbg = e ? atoi(e) : 0; }
-        bt.prof = nullptr;
-        if (bt.dbg & 2048) { if (int s = phz_reserve(ctx, S[SC_MAP_PROFILE], (size_t)ntiles * 64)) return s; bt.prof = (unsigned long long *)S[SC_MAP_PROFILE].p; }
-        hipLaunchKernelGGL(k_tile_window, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, sm, bt, tile_reads);
-        PHZ_HIP(ctx, hipEventRecord(ctx->map_ev[0], sm));
-        unsigned dyn_lds = 0;          // experiment: dynamic LDS nobody uses, to bound the workgroups per CU (PHZ_MAP_DYNLDS bytes)
-        { const char *e = getenv("PHZ_MAP_DYNLDS"); if (e && atoi(e) > 0) dyn_lds = (unsigned)atoi(e); }
-#define PHZ_LAUNCH_MAP(B, R) do { if (bt.dbg) hipLaunchKernelGGL((k_map<B, R, true>), dim3((unsigned)ntiles), dim3(B), dyn_lds, sm, bt); \
-                                 else if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true>), dim3((unsigned)ntiles), dim3(B), dyn_lds, sm, bt); \
-                                 else hipLaunchKernelGGL((k_map<B, R, false>), dim3((unsigned)ntiles), dim3(B), dyn_lds, sm, bt); } while (0)
-        if (blk == 128) PHZ_LAUNCH_MAP(128, 2);
-        else PHZ_LAUNCH_MAP(256, 2);
-#undef PHZ_LAUNCH_MAP
-        PHZ_HIP(ctx, hipEventRecord(ctx->map_ev[1], sm));
-        hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)nchunks), dim3(1024), 0, sm, (const int32_t *)S[SC_MAP_TILE_TOTAL].p, ntiles, tile_pref, chunk_sum,
-                           chunk_max);
-        hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(1024), 0, sm, (const int64_t *)chunk_sum, (const int32_t *)chunk_max, nchunks, chunk_base,
-                           (unsigned long long *)ctx->scalars.p);
-        hipLaunchKernelGGL(k_shard_totals, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, sm, d_tile0, m, ntiles, (const int32_t *)tile_pref,
-                           (const int64_t *)chunk_base, (unsigned long long *)ctx->scalars.p, d_shard_base);
-        CompactArgs c;
-        c.stage = bt.stage; c.side = bt.side; c.slots = bt.slots;
-        c.shards = d_shards; c.tile0 = d_tile0; c.n_shards = m;
-        c.tile_total = (const int32_t *)S[SC_MAP_TILE_TOTAL].p; c.tile_pref = tile_pref; c.chunk_base = chunk_base; c.shard_base = d_shard_base;
-        c.tile_w0 = bt.tile_w0;
-        c.slot_cap = slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = (const uint32_t *)S[SC_MAP_TILE_OVF].p;
-        hipLaunchKernelGGL(k_compact, dim3((unsigned)((ntiles + 4 * CT - 1) / (4 * CT))), dim3(256), 0, sm, c);
-        PHZ_HIP(ctx, hipGetLastError());
-        PHZ_HIP(ctx, hipMemcpyAsync(scal, ctx->scalars.p, (size_t)8 * (m + 3), hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipStreamSynchronize(sm));
-        float ms = 0;
-        PHZ_HIP(ctx, hipEventElapsedTime(&ms, ctx->map_ev[0], ctx->map_ev[1]));
-        if (bt.prof) {          // mean time between the stamps of a tile (wall_clock64: 100 MHz), first wave's view
-            std::vector<unsigned long long> pr((size_t)ntiles * 8);
-            PHZ_HIP(ctx, hipMemcpy(pr.data(), bt.prof, pr.size() * 8, hipMemcpyDeviceToHost));
-            double seg[7] = {0, 0, 0, 0, 0, 0, 0}; double life = 0;
-            for (int64_t t = 0; t < ntiles; t++) { for (int k = 0; k < 7; k++) seg[k] += (double)(pr[8 * t + k + 1] - pr[8 * t + k]); life += (double)(pr[8 * t + 7] - pr[8 * t]); }
-            fprintf(stderr, "[k_map profile] %lld tiles, kernel %.3f ms, tile lifetime %.2f us: stage loads -> LDS %.2f | single-run records + first gathers %.2f | barrier %.2f | "
-                            "multi-op walk %.2f | candidate gathers + resolve %.2f | scan %.2f | flush %.2f us\n", (long long)ntiles, ms, life / ntiles / 100.0,
-                    seg[0] / ntiles / 100.0, seg[1] / ntiles / 100.0, seg[2] / ntiles / 100.0, seg[3] / ntiles / 100.0, seg[4] / ntiles / 100.0, seg[5] / ntiles / 100.0, seg[6] / ntiles / 100.0);
-        }
-        ms_total += ms;
-        if ((int64_t)scal[2 + m] <= ctx->map_ovf_cap) break;          // every dense tile found room
-        if (attempt == 2) return phz_fail(ctx, PHZ_E_HIP, "K_map staging overflow area did not converge");
-        ctx->map_ovf_cap = (int64_t)scal[2 + m] + (int64_t)(scal[2 + m] / 16) + 4096;      // the calls of all dense tiles (+ slack for the next submission): redo the batch
-    }
-    ctx->last_ms[PHZ_T_MAP] = ms_total; ctx->total_ms[PHZ_T_MAP] += ms_total; ctx->launches[PHZ_T_MAP]++;
-    int st = PHZ_OK;
-    for (int k = 0; k < m; k++) {
-        const int i = live[(size_t)k];
-        n_calls[i] = (int64_t)scal[2 + k];
-        if (n_calls[i] > out[i].cap) st = PHZ_E_CAPACITY;
-    }
-    return st;
 }
 
 int phz_launch_map(phz_ctx *ctx, const phz_reads &r, const phz_variants &v, int baseq, const phz_calls &out,

@@ -2,12 +2,6 @@
 // launchers of phz_map.hip.
 #include "phz_internal.h"
 
-static int upload(phz_ctx *ctx, DevBuf &b, const void *src, size_t bytes) {
-    if (int s = phz_reserve(ctx, b, bytes ? bytes : 1)) return s;
-    if (bytes) PHZ_HIP(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return PHZ_OK;
-}
-
 static int check_variants(phz_ctx *ctx, const phz_variants *v, int space) {
     // SNP-only fast path: reject indel mode up front (host-visible arrays only)
     if (space == PHZ_HOST && v->ref_len)
@@ -36,34 +30,30 @@ extern "C" int phz_map_reads(phz_ctx *ctx, const phz_reads *reads, const phz_var
     if (space == PHZ_DEVICE) return phz_launch_map(ctx, *reads, *vars, baseq, *out, n_calls);
     if (space != PHZ_HOST) return phz_fail(ctx, PHZ_E_ARG, "bad memory space");
 
-    const int64_t n = reads->n_reads;
+    // device copies of the caller's arrays and outputs: slots of the ctx's staging pool, as for every other PHZ_HOST entry point
+    Staging st(ctx);
+    const size_t n = (size_t)reads->n_reads, cap = (size_t)out->cap;
     phz_reads dr = *reads;
     phz_variants dv = *vars;
-    if (int s = upload(ctx, ctx->r_pos, reads->pos, (size_t)n * 4)) return s;
-    if (int s = upload(ctx, ctx->r_coff, reads->cigar_off, (size_t)(n + 1) * 4)) return s;
-    if (int s = upload(ctx, ctx->r_cig, reads->cigar, (size_t)reads->n_ops * 4)) return s;
-    if (int s = upload(ctx, ctx->r_soff, reads->seq_off, (size_t)(n + 1) * 4)) return s;
-    if (int s = upload(ctx, ctx->r_seq, reads->seq2, (size_t)reads->n_seq_bytes)) return s;
-    if (int s = upload(ctx, ctx->r_qual, reads->qual, (size_t)reads->n_seq_bytes * 4)) return s;
-    if (int s = upload(ctx, ctx->v_pos, vars->pos, (size_t)vars->n * 4)) return s;
-    dr.pos = (const int32_t *)ctx->r_pos.p; dr.cigar_off = (const uint32_t *)ctx->r_coff.p;
-    dr.cigar = (const uint32_t *)ctx->r_cig.p; dr.seq_off = (const uint32_t *)ctx->r_soff.p;
-    dr.seq2 = (const uint8_t *)ctx->r_seq.p; dr.qual = (const uint8_t *)ctx->r_qual.p; dr.bq = nullptr;
-    dv.pos = (const int32_t *)ctx->v_pos.p; dv.ref_len = nullptr;
-    phz_calls dc;
-    dc.cap = out->cap;
-    const size_t cap = (size_t)(out->cap ? out->cap : 1);
-    if (int s = phz_reserve(ctx, ctx->c_read, cap * 4)) return s;
-    if (int s = phz_reserve(ctx, ctx->c_var, cap * 4)) return s;
-    if (int s = phz_reserve(ctx, ctx->c_code, cap)) return s;
-    if (int s = phz_reserve(ctx, ctx->c_aux0, cap * 4)) return s;
-    if (int s = phz_reserve(ctx, ctx->c_aux1, cap * 4)) return s;
-    dc.read_idx = (int32_t *)ctx->c_read.p; dc.var_idx = (int32_t *)ctx->c_var.p; dc.code = (uint8_t *)ctx->c_code.p;
-    dc.aux0 = (uint32_t *)ctx->c_aux0.p; dc.aux1 = (uint32_t *)ctx->c_aux1.p;
-    if (!out->aux0 || !out->aux1) { dc.aux0 = nullptr; dc.aux1 = nullptr; }
-    int st = phz_launch_map(ctx, dr, dv, baseq, dc, n_calls);
-    if (st != PHZ_OK && st != PHZ_E_CAPACITY) return st;
-    const size_t m = (size_t)(*n_calls < out->cap ? *n_calls : out->cap);
+    phz_calls dc = *out;
+    dr.bq = nullptr; dv.ref_len = nullptr; dc.aux0 = nullptr; dc.aux1 = nullptr;
+    if (int s = st.in(reads->pos, n, space, &dr.pos)) return s;
+    if (int s = st.in(reads->cigar_off, n + 1, space, &dr.cigar_off)) return s;
+    if (int s = st.in(reads->cigar, (size_t)reads->n_ops, space, &dr.cigar)) return s;
+    if (int s = st.in(reads->seq_off, n + 1, space, &dr.seq_off)) return s;
+    if (int s = st.in(reads->seq2, (size_t)reads->n_seq_bytes, space, &dr.seq2)) return s;
+    if (int s = st.in(reads->qual, (size_t)reads->n_seq_bytes * 4, space, &dr.qual)) return s;
+    if (int s = st.in(vars->pos, (size_t)vars->n, space, &dv.pos)) return s;
+    if (int s = st.out(out->read_idx, cap, space, &dc.read_idx)) return s;
+    if (int s = st.out(out->var_idx, cap, space, &dc.var_idx)) return s;
+    if (int s = st.out(out->code, cap, space, &dc.code)) return s;
+    if (out->aux0 && out->aux1) {          // both planes or none
+        if (int s = st.out(out->aux0, cap, space, &dc.aux0)) return s;
+        if (int s = st.out(out->aux1, cap, space, &dc.aux1)) return s;
+    }
+    const int status = phz_launch_map(ctx, dr, dv, baseq, dc, n_calls);
+    if (status != PHZ_OK && status != PHZ_E_CAPACITY) return status;
+    const size_t m = (size_t)(*n_calls < out->cap ? *n_calls : out->cap);          // PHZ_E_CAPACITY: the first `cap` calls
     if (m) {
         PHZ_HIP(ctx, hipMemcpyAsync(out->read_idx, dc.read_idx, m * 4, hipMemcpyDeviceToHost, ctx->stream));
         PHZ_HIP(ctx, hipMemcpyAsync(out->var_idx, dc.var_idx, m * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -74,5 +64,5 @@ extern "C" int phz_map_reads(phz_ctx *ctx, const phz_reads *reads, const phz_var
         }
     }
     PHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return st;
+    return status;
 }

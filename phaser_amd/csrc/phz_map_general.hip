@@ -531,6 +531,125 @@ __global__ __launch_bounds__(256) void k_map_general_list(GenArgs a) {
     }
 }
 
+// What one phz_map_reads_general call knows; its functions are the sections of the call in stream order.
+struct GenCall {
+    phz_ctx *ctx; hipStream_t sm; DevBuf *S; Staging st; const int space;
+    GenArgs a; const int64_t n, nv; const unsigned grid;          // (grid: tiles of GEN_TILE records)
+    uint32_t *cb, *tb;          // exclusive scans of the tiles' calls / text characters; [grid]: the totals
+    uint32_t n_listed = 0; int64_t total = 0, ttotal = 0;          // read back by totals()
+
+    GenCall(phz_ctx *c, int64_t n_, int64_t nv_, int baseq, int space_)
+        : ctx(c), sm(c->stream), S(c->scratch), st(c), space(space_), n(n_), nv(nv_), grid((unsigned)((n_ + GEN_TILE - 1) / GEN_TILE)) {
+        memset(&a, 0, sizeof a);
+        a.n = n; a.nv = (int)nv; a.baseq = baseq;
+    }
+    template <class T> T *scr(int slot) const { return (T *)S[slot].p; }
+
+    // ---- the caller's arrays on the device
+    int stage_inputs(const phz_reads *reads, const phz_variants_general *vars) {
+        if (int s = st.in(reads->pos, (size_t)n, space, &a.pos)) return s;
+        if (int s = st.in(reads->cigar_off, (size_t)n + 1, space, &a.cigar_off)) return s;
+        if (int s = st.in(reads->cigar, (size_t)reads->n_ops, space, &a.cigar)) return s;
+        if (int s = st.in(reads->seq_off, (size_t)n + 1, space, &a.seq_off)) return s;
+        if (int s = st.in(reads->seq2, (size_t)reads->n_seq_bytes, space, &a.seq2)) return s;
+        if (int s = st.in(reads->qual, (size_t)reads->n_seq_bytes * 4, space, &a.qual)) return s;
+        if (int s = st.in(vars->pos, (size_t)nv, space, &a.vpos)) return s;
+        if (int s = st.in(vars->ref_len, (size_t)nv, space, &a.ref_len)) return s;
+        if (int s = st.in(vars->allele_off, (size_t)nv * 2 + 1, space, &a.aoff)) return s;
+        return st.in(vars->allele_bytes, (size_t)vars->n_allele_bytes, space, &a.abytes);
+    }
+    // ---- the scratch of both passes; SC_GEN_TILE_SUMS: [tile_calls x grid][tile_text x grid][cb x (grid+1)][tb x (grid+1)]
+    int reserve() {
+        if (n >= (1ll << 32)) return phz_fail(ctx, PHZ_E_ARG, "too many records in one shard");
+        const size_t N = (size_t)n;
+        if (int s = reserve_all(ctx, {{S[SC_GEN_N_CALLS], N * 4}, {S[SC_GEN_TILE_SUMS], (size_t)(grid + 1) * 16}, {S[SC_GEN_CALL_BASE], N * 4}, {S[SC_GEN_TEXT_BASE], N * 4},
+                                      {S[SC_GEN_WINDOW], (size_t)grid * 8}, {S[SC_GEN_DESC], (size_t)nv * 4}, {S[SC_GEN_WORKLIST], N * 4}, {S[SC_GEN_WORKLIST_N], 64},
+                                      {S[SC_GEN_SIDE], N * 16}})) return s;
+        a.n_calls = scr<uint32_t>(SC_GEN_N_CALLS);
+        a.tile_calls = scr<uint32_t>(SC_GEN_TILE_SUMS); a.tile_text = a.tile_calls + grid;
+        cb = a.tile_text + grid; tb = cb + grid + 1;
+        a.tile_cbase = cb; a.tile_tbase = tb;
+        a.call_base = scr<uint32_t>(SC_GEN_CALL_BASE); a.text_base = scr<uint32_t>(SC_GEN_TEXT_BASE);
+        a.side = scr<uint4>(SC_GEN_SIDE);
+        a.win = scr<const int32_t>(SC_GEN_WINDOW); a.desc = scr<const uint32_t>(SC_GEN_DESC);
+        a.wl = scr<uint32_t>(SC_GEN_WORKLIST); a.wl_n = scr<uint32_t>(SC_GEN_WORKLIST_N);
+        return PHZ_OK;
+    }
+    // ---- windows, variant descriptors, the count pass and its list pass, the two scans of the tile sums
+    int count_and_scan() {
+        PHZ_HIP(ctx, hipMemsetAsync(a.wl_n, 0, 4, sm));
+        PHZ_HIP(ctx, hipEventRecord(ctx->ev0, sm));
+        hipLaunchKernelGGL(k_gen_window, dim3((grid + 255) / 256), dim3(256), 0, sm, a.pos, n, GEN_TILE, a.vpos, (int)nv, (int64_t)grid, scr<int32_t>(SC_GEN_WINDOW));
+        hipLaunchKernelGGL(k_gen_desc, dim3(nblk(nv)), dim3(256), 0, sm, a.ref_len, a.aoff, a.abytes, (int)nv, scr<uint32_t>(SC_GEN_DESC));
+        hipLaunchKernelGGL(k_map_general, dim3(grid), dim3(256), 0, sm, a);
+        hipLaunchKernelGGL(k_map_general_list<false>, dim3(2048), dim3(256), 0, sm, a);     // grid-stride over a list whose length only the device knows
+        if (int s = scan_excl(ctx, a.tile_calls, cb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
+        return scan_excl(ctx, a.tile_text, tb, (int64_t)grid, S[SC_GEN_SCAN_TMP]);
+    }
+    // ---- WAIT: the list length and the two totals as one PhzMail block; the caller's counts, the PHZ_GEN_DBG line, the time of a call whose emit pass is already
+    // behind it (`emitted`), and PHZ_E_CAPACITY when an output is too small for the totals
+    int totals(bool emitted, const phz_calls *out, const uint32_t *text_roff, int64_t text_cap, int64_t *n_calls, int64_t *n_text) {
+        PhzMail mail(ctx);
+        const int k_listed = mail.add(a.wl_n, 4), k_calls = mail.add(cb + grid, 4), k_text = mail.add(tb + grid, 4);
+        if (int s = mail.send()) return s;
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        n_listed = *mail.at<uint32_t>(k_listed); total = (int64_t)*mail.at<uint32_t>(k_calls); ttotal = (int64_t)*mail.at<uint32_t>(k_text);
+        if (getenv("PHZ_GEN_DBG")) fprintf(stderr, "K_map_general: %lld records, %u handed to the list, %lld calls, %lld text\n", (long long)n, n_listed, (long long)total, (long long)ttotal);
+        *n_calls = total;
+        if (n_text) *n_text = ttotal;
+        if (emitted) if (int s = book_time()) return s;
+        return total > out->cap || (text_roff && ttotal > text_cap) ? PHZ_E_CAPACITY : PHZ_OK;
+    }
+    int book_time() {
+        float ms = 0;
+        PHZ_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        ctx->last_ms[PHZ_T_MAP] = ms; ctx->total_ms[PHZ_T_MAP] += ms; ctx->launches[PHZ_T_MAP]++;
+        return PHZ_OK;
+    }
+    // ---- the emit pass into a.o_*: the fast records, then the list -- over `list_grid` workgroups --, the end of the timed span
+    int emit(unsigned list_grid) {
+        hipLaunchKernelGGL(k_gen_emit, dim3(grid), dim3(256), 0, sm, a);
+        if (list_grid) hipLaunchKernelGGL(k_map_general_list<true>, dim3(list_grid), dim3(256), 0, sm, a);
+        if (space == PHZ_DEVICE && a.o_text_off) hipLaunchKernelGGL(k_gen_tail, dim3(1), dim3(1), 0, sm, (const uint32_t *)(cb + grid), (const uint32_t *)(tb + grid), a.o_text_off, a.cap);
+        PHZ_HIP(ctx, hipGetLastError());
+        PHZ_HIP(ctx, hipEventRecord(ctx->ev1, sm));
+        return PHZ_OK;
+    }
+    // ---- PHZ_HOST: device copies of the outputs, sized by the caller's capacities
+    int stage_outputs(phz_calls *out, uint32_t *call_text_off, uint32_t *text_roff, int64_t text_cap) {
+        const size_t cap = (size_t)out->cap;
+        if (int s = st.out(out->read_idx, cap, space, &a.o_read)) return s;
+        if (int s = st.out(out->var_idx, cap, space, &a.o_var)) return s;
+        if (int s = st.out(out->code, cap, space, &a.o_code)) return s;
+        if (int s = st.out(out->aux0, cap, space, &a.o_aux0)) return s;
+        if (int s = st.out(out->aux1, cap, space, &a.o_aux1)) return s;
+        if (call_text_off && text_roff) {
+            if (int s = st.out(call_text_off, cap + 1, space, &a.o_text_off)) return s;
+            if (int s = st.out(text_roff, (size_t)(text_cap ? text_cap : 1), space, &a.o_text)) return s;
+        }
+        a.cap = out->cap; a.text_cap = text_cap;
+        return PHZ_OK;
+    }
+    // ---- PHZ_HOST: the terminator of the text offsets, the lists back to the caller.  WAIT
+    int copy_out(phz_calls *out, uint32_t *call_text_off, uint32_t *text_roff) {
+        const size_t T = (size_t)total;
+        if (a.o_text_off) { const uint32_t tt = (uint32_t)ttotal; PHZ_HIP(ctx, hipMemcpyAsync(a.o_text_off + total, &tt, 4, hipMemcpyHostToDevice, sm)); }
+        if (space == PHZ_HOST && total) {
+            PHZ_HIP(ctx, hipMemcpyAsync(out->read_idx, a.o_read, T * 4, hipMemcpyDeviceToHost, sm));
+            PHZ_HIP(ctx, hipMemcpyAsync(out->var_idx, a.o_var, T * 4, hipMemcpyDeviceToHost, sm));
+            PHZ_HIP(ctx, hipMemcpyAsync(out->code, a.o_code, T, hipMemcpyDeviceToHost, sm));
+            PHZ_HIP(ctx, hipMemcpyAsync(out->aux0, a.o_aux0, T * 4, hipMemcpyDeviceToHost, sm));
+            PHZ_HIP(ctx, hipMemcpyAsync(out->aux1, a.o_aux1, T * 4, hipMemcpyDeviceToHost, sm));
+            if (a.o_text_off) {
+                PHZ_HIP(ctx, hipMemcpyAsync(call_text_off, a.o_text_off, (T + 1) * 4, hipMemcpyDeviceToHost, sm));
+                if (ttotal) PHZ_HIP(ctx, hipMemcpyAsync(text_roff, a.o_text, (size_t)ttotal * 4, hipMemcpyDeviceToHost, sm));
+            }
+        }
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        return book_time();
+    }
+};
+
 }  // namespace
 
 extern "C" int phz_map_reads_general(phz_ctx *ctx, const phz_reads *reads, const phz_variants_general *vars, int baseq,
@@ -541,116 +660,24 @@ extern "C" int phz_map_reads_general(phz_ctx *ctx, const phz_reads *reads, const
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     *n_calls = 0;
     if (n_text) *n_text = 0;
-    const int64_t n = reads->n_reads, nv = vars->n;
-    if (n == 0 || nv == 0) return PHZ_OK;
-    if (nv > 0x7fffffff) return phz_fail(ctx, PHZ_E_ARG, "too many variants in one shard");
-    Staging st(ctx);
-    GenArgs a;
-    memset(&a, 0, sizeof a);
-    if (int s = st.in(reads->pos, (size_t)n, space, &a.pos)) return s;
-    if (int s = st.in(reads->cigar_off, (size_t)n + 1, space, &a.cigar_off)) return s;
-    if (int s = st.in(reads->cigar, (size_t)reads->n_ops, space, &a.cigar)) return s;
-    if (int s = st.in(reads->seq_off, (size_t)n + 1, space, &a.seq_off)) return s;
-    if (int s = st.in(reads->seq2, (size_t)reads->n_seq_bytes, space, &a.seq2)) return s;
-    if (int s = st.in(reads->qual, (size_t)reads->n_seq_bytes * 4, space, &a.qual)) return s;
-    if (int s = st.in(vars->pos, (size_t)nv, space, &a.vpos)) return s;
-    if (int s = st.in(vars->ref_len, (size_t)nv, space, &a.ref_len)) return s;
-    if (int s = st.in(vars->allele_off, (size_t)nv * 2 + 1, space, &a.aoff)) return s;
-    if (int s = st.in(vars->allele_bytes, (size_t)vars->n_allele_bytes, space, &a.abytes)) return s;
-    a.n = n; a.nv = (int)nv; a.baseq = baseq;
-    DevBuf *S = ctx->scratch;
-    if (int s = phz_reserve(ctx, S[SC_GEN_N_CALLS], (size_t)n * 4)) return s;
-    const unsigned grid = (unsigned)((n + GEN_TILE - 1) / GEN_TILE);
-    if (int s = phz_reserve(ctx, S[SC_GEN_TILE_SUMS], (size_t)(grid + 1) * 16)) return s;
-    if (int s = phz_reserve(ctx, S[SC_GEN_CALL_BASE], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[SC_GEN_TEXT_BASE], (size_t)n * 4)) return s;
-    a.n_calls = (uint32_t *)S[SC_GEN_N_CALLS].p;
-    a.tile_calls = (uint32_t *)S[SC_GEN_TILE_SUMS].p; a.tile_text = a.tile_calls + grid;
-    uint32_t *cb = a.tile_text + grid, *tb = cb + grid + 1;
-    a.tile_cbase = cb; a.tile_tbase = tb;
-    a.call_base = (uint32_t *)S[SC_GEN_CALL_BASE].p; a.text_base = (uint32_t *)S[SC_GEN_TEXT_BASE].p;
-    hipStream_t sm = ctx->stream;
-    if (int s = phz_reserve(ctx, S[SC_GEN_WINDOW], (size_t)grid * 8)) return s;
-    if (int s = phz_reserve(ctx, S[SC_GEN_DESC], (size_t)nv * 4)) return s;
-    if (n >= (1ll << 32)) return phz_fail(ctx, PHZ_E_ARG, "too many records in one shard");
-    if (int s = phz_reserve(ctx, S[SC_GEN_WORKLIST], (size_t)n * 4)) return s;
-    if (int s = phz_reserve(ctx, S[SC_GEN_WORKLIST_N], 64)) return s;
-    if (int s = phz_reserve(ctx, S[SC_GEN_SIDE], (size_t)n * 16)) return s;
-    a.side = (uint4 *)S[SC_GEN_SIDE].p;
-    a.win = (const int32_t *)S[SC_GEN_WINDOW].p; a.desc = (const uint32_t *)S[SC_GEN_DESC].p;
-    a.wl = (uint32_t *)S[SC_GEN_WORKLIST].p; a.wl_n = (uint32_t *)S[SC_GEN_WORKLIST_N].p;
-    PHZ_HIP(ctx, hipMemsetAsync(a.wl_n, 0, 4, sm));
-    PHZ_HIP(ctx, hipEventRecord(ctx->ev0, sm));
-    hipLaunchKernelGGL(k_gen_window, dim3((grid + 255) / 256), dim3(256), 0, sm, a.pos, n, GEN_TILE, a.vpos, (int)nv, (int64_t)grid, (int32_t *)S[SC_GEN_WINDOW].p);
-    hipLaunchKernelGGL(k_gen_desc, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, sm, a.ref_len, a.aoff, a.abytes, (int)nv, (uint32_t *)S[SC_GEN_DESC].p);
-    hipLaunchKernelGGL(k_map_general, dim3(grid), dim3(256), 0, sm, a);
-    hipLaunchKernelGGL(k_map_general_list<false>, dim3(2048), dim3(256), 0, sm, a);     // grid-stride over a list whose length only the device knows
-    if (int s = scan_excl(ctx, a.tile_calls, cb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
-    if (int s = scan_excl(ctx, a.tile_text, tb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
-    uint32_t last[2], n_listed = 0;
+    if (reads->n_reads == 0 || vars->n == 0) return PHZ_OK;
+    if (vars->n > 0x7fffffff) return phz_fail(ctx, PHZ_E_ARG, "too many variants in one shard");
+    GenCall g(ctx, reads->n_reads, vars->n, baseq, space);
+    if (int s = g.stage_inputs(reads, vars)) return s;
+    if (int s = g.reserve()) return s;
+    if (int s = g.count_and_scan()) return s;
     if (space == PHZ_DEVICE) {
         // device-resident outputs already exist at their capacity: nothing on the host has to know the totals before the emit
         // kernels run (every store is bounded by cap / text_cap), so the whole call is queued at once and waited for once
+        GenArgs &a = g.a;
         a.o_read = out->read_idx; a.o_var = out->var_idx; a.o_code = out->code; a.o_aux0 = out->aux0; a.o_aux1 = out->aux1;
         a.o_text_off = (call_text_off && text_roff) ? call_text_off : nullptr; a.o_text = (call_text_off && text_roff) ? text_roff : nullptr;
         a.cap = out->cap; a.text_cap = text_cap;
-        hipLaunchKernelGGL(k_gen_emit, dim3(grid), dim3(256), 0, sm, a);
-        hipLaunchKernelGGL(k_map_general_list<true>, dim3(2048), dim3(256), 0, sm, a);
-        if (a.o_text_off) hipLaunchKernelGGL(k_gen_tail, dim3(1), dim3(1), 0, sm, (const uint32_t *)(cb + grid), (const uint32_t *)(tb + grid), a.o_text_off, a.cap);
-        PHZ_HIP(ctx, hipGetLastError());
-        PHZ_HIP(ctx, hipEventRecord(ctx->ev1, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(&n_listed, a.wl_n, 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(&last[0], cb + grid, 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(&last[1], tb + grid, 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipStreamSynchronize(sm));
-        if (getenv("PHZ_GEN_DBG")) fprintf(stderr, "K_map_general: %lld records, %u handed to the list, %u calls, %u text\n", (long long)n, n_listed, last[0], last[1]);
-        *n_calls = (int64_t)last[0];
-        if (n_text) *n_text = (int64_t)last[1];
-        float ms = 0;
-        PHZ_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        ctx->last_ms[PHZ_T_MAP] = ms; ctx->total_ms[PHZ_T_MAP] += ms; ctx->launches[PHZ_T_MAP]++;
-        if ((int64_t)last[0] > out->cap || (text_roff && (int64_t)last[1] > text_cap)) return PHZ_E_CAPACITY;
-        return PHZ_OK;
+        if (int s = g.emit(2048)) return s;
+        return g.totals(true, out, text_roff, text_cap, n_calls, n_text);
     }
-    PHZ_HIP(ctx, hipMemcpyAsync(&n_listed, a.wl_n, 4, hipMemcpyDeviceToHost, sm));
-    PHZ_HIP(ctx, hipMemcpyAsync(&last[0], cb + grid, 4, hipMemcpyDeviceToHost, sm));
-    PHZ_HIP(ctx, hipMemcpyAsync(&last[1], tb + grid, 4, hipMemcpyDeviceToHost, sm));
-    PHZ_HIP(ctx, hipStreamSynchronize(sm));
-    const int64_t total = (int64_t)last[0], ttotal = (int64_t)last[1];
-    if (getenv("PHZ_GEN_DBG")) fprintf(stderr, "K_map_general: %lld records, %u handed to the list, %lld calls, %lld text\n", (long long)n, n_listed, (long long)total, (long long)ttotal);
-    *n_calls = total;
-    if (n_text) *n_text = ttotal;
-    if (total > out->cap || (text_roff && ttotal > text_cap)) return PHZ_E_CAPACITY;
-    uint32_t *d_toff = nullptr, *d_text = nullptr;
-    if (int s = st.out(out->read_idx, (size_t)out->cap, space, &a.o_read)) return s;
-    if (int s = st.out(out->var_idx, (size_t)out->cap, space, &a.o_var)) return s;
-    if (int s = st.out(out->code, (size_t)out->cap, space, &a.o_code)) return s;
-    if (int s = st.out(out->aux0, (size_t)out->cap, space, &a.o_aux0)) return s;
-    if (int s = st.out(out->aux1, (size_t)out->cap, space, &a.o_aux1)) return s;
-    if (call_text_off && text_roff) {
-        if (int s = st.out(call_text_off, (size_t)out->cap + 1, space, &d_toff)) return s;
-        if (int s = st.out(text_roff, (size_t)(text_cap ? text_cap : 1), space, &d_text)) return s;
-    }
-    a.o_text_off = d_toff; a.o_text = d_text; a.cap = out->cap; a.text_cap = text_cap;
-    hipLaunchKernelGGL(k_gen_emit, dim3(grid), dim3(256), 0, sm, a);
-    if (n_listed) hipLaunchKernelGGL(k_map_general_list<true>, dim3((n_listed + 255) / 256), dim3(256), 0, sm, a);
-    PHZ_HIP(ctx, hipGetLastError());
-    PHZ_HIP(ctx, hipEventRecord(ctx->ev1, sm));
-    if (d_toff) { const uint32_t tt = (uint32_t)ttotal; PHZ_HIP(ctx, hipMemcpyAsync(d_toff + total, &tt, 4, hipMemcpyHostToDevice, sm)); }
-    if (space == PHZ_HOST && total) {
-        PHZ_HIP(ctx, hipMemcpyAsync(out->read_idx, a.o_read, (size_t)total * 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(out->var_idx, a.o_var, (size_t)total * 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(out->code, a.o_code, (size_t)total, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(out->aux0, a.o_aux0, (size_t)total * 4, hipMemcpyDeviceToHost, sm));
-        PHZ_HIP(ctx, hipMemcpyAsync(out->aux1, a.o_aux1, (size_t)total * 4, hipMemcpyDeviceToHost, sm));
-        if (d_toff) {
-            PHZ_HIP(ctx, hipMemcpyAsync(call_text_off, d_toff, ((size_t)total + 1) * 4, hipMemcpyDeviceToHost, sm));
-            if (ttotal) PHZ_HIP(ctx, hipMemcpyAsync(text_roff, d_text, (size_t)ttotal * 4, hipMemcpyDeviceToHost, sm));
-        }
-    }
-    PHZ_HIP(ctx, hipStreamSynchronize(sm));
-    float ms = 0;
-    PHZ_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms[PHZ_T_MAP] = ms; ctx->total_ms[PHZ_T_MAP] += ms; ctx->launches[PHZ_T_MAP]++;
-    return PHZ_OK;
+    if (int s = g.totals(false, out, text_roff, text_cap, n_calls, n_text)) return s;          // (PHZ_E_CAPACITY: nothing is emitted)
+    if (int s = g.stage_outputs(out, call_text_off, text_roff, text_cap)) return s;
+    if (int s = g.emit((g.n_listed + 255) / 256)) return s;
+    return g.copy_out(out, call_text_off, text_roff);
 }

@@ -458,3 +458,196 @@ def test_resident_variant_table(mapper, oracle_build):
     bad = np.array([5, 3], dtype=np.int32); one = np.ones(2, dtype=np.uint8); out = _lib.phz_variants()
     import ctypes as C
     assert mapper.ctx.lib.phz_load_variants(mapper.ctx.h, 1, C.c_void_p(bad.ctypes.data), C.c_void_p(one.ctypes.data), 2, _lib.PHZ_HOST, C.byref(out)) == _lib.PHZ_E_ARG
+
+
+# ---- the host drivers of K_map / K_map_general: what a ctx keeps between submissions and what its entry points share.  Shards of ~1,500 read pairs over 40-400
+# het SNPs (tiles of 256 records: at least three, the last one partial), their oracle lists computed once
+@pytest.fixture(scope="module")
+def small_shards(oracle_build):
+    from phaser_amd import soa, synth
+    out = []
+    for seed, n_pairs, n_snps in ((701, 1500, 40), (702, 1500, 400), (703, 1400, 120), (704, 1600, 250), (705, 450, 60)):
+        v, gs, ge, w = synth.make_variants("chr1", 1, 30_000_000, n_snps, seed, n_genes=max(4, n_snps // 25))
+        rb = synth.make_reads(v, gs, ge, w, n_pairs, seed + 100, n_rate=0.002)
+        rb = rb.select(synth.samtools_keep(rb, 255))
+        host = soa.pack_readbatch(rb)
+        assert host.n >= 3 * 256 + 1 or n_pairs < 1000
+        out.append({"rb": rb, "host": host, "dev": host.to("cuda"), "vpos": v.pos.to(torch.int32).contiguous(), "v": v,
+                    "want": oracle_map_readbatch(oracle_build, rb, v.pos.numpy(), 10)})
+    return out
+
+
+def _same_lists(calls, want, n=None):
+    c = calls.cpu()
+    o_r, o_v, o_c = want[0], want[1], want[2]
+    n = len(o_r) if n is None else n
+    assert c.n == n
+    assert np.array_equal(c.read_idx.numpy(), o_r[:n]) and np.array_equal(c.var_idx.numpy(), o_v[:n]) and np.array_equal(c.code.numpy(), o_c[:n])
+
+
+def _same_text(sh, aux0, aux1, baseq=10):
+    """the two text planes of the code-4 calls against the oracle's allele texts"""
+    from phaser_amd.read_variant_map import _allele_text
+    o_r, _, o_c, o_t = sh["want"]
+    rb = sh["rb"]; lut = "ACGTN"
+    for k in np.nonzero(o_c == 4)[0]:
+        r = int(o_r[k])
+        seq = "".join(lut[x] for x in rb.seq[r].tolist()); qual = "".join(chr(33 + q) for q in rb.qual[r].tolist())
+        assert _allele_text(4, int(aux0[k]) & 0xFFFFFFFF, int(aux1[k]) & 0xFFFFFFFF, seq, qual, baseq) == o_t[k]
+
+
+def _submit(m, shards, caps=None, aux=True):
+    """one phz_map_reads_batch over device shards into fresh output buffers -> (status, [Calls cut to min(n_calls, cap)], [n_calls])"""
+    from phaser_amd.mapper import Calls
+    caps = caps or [len(s["want"][0]) + 8 for s in shards]
+    call, bufs, N = m.prepare_batch([s["dev"] for s in shards], [s["vpos"] for s in shards], 10, caps, aux)
+    torch.cuda.synchronize()
+    st = call()
+    m.ctx.check(st, allow=(-3,))
+    return st, [Calls(*[None if t is None else t[:min(int(N[i]), caps[i])] for t in bufs[i]]) for i in range(len(shards))], [int(N[i]) for i in range(len(shards))]
+
+
+def test_percentile_enqueued_then_a_mapping_on_one_ctx(small_shards):
+    """phz_as_cutoff_enqueue returns with the upload of its shard table still queued (the engine's close_bam of one BAM); the next call on the ctx maps the
+    following BAM.  K_map builds its table in a pinned image of its own, so the percentile's kernels read their table whatever the timing: the cutoff block is
+    the one of the same enqueue alone on a fresh ctx, and the call lists are the oracle's.  (Run once: the order of the two calls is the case, not a race won.)"""
+    import ctypes as C
+    from phaser_amd import _lib
+    from phaser_amd.mapper import Calls, Mapper
+    g = torch.Generator().manual_seed(71)
+    n_reads, n_lines = 1000, 2000
+    as16 = torch.randint(-60, 1, (n_reads,), generator=g, dtype=torch.int16)
+    as16[torch.rand(n_reads, generator=g) < 0.2] = -32768                     # records without an AS tag
+    read_idx = torch.sort(torch.randint(0, n_reads, (n_lines,), generator=g, dtype=torch.int32)).values
+    dev = {"as16": as16.cuda(), "read_idx": read_idx.cuda(), "z32": torch.zeros(n_lines, dtype=torch.int32, device="cuda"),
+           "z8": torch.zeros(n_lines, dtype=torch.uint8, device="cuda"), "qid": torch.zeros(n_reads, dtype=torch.int32, device="cuda")}
+    p = lambda t: C.c_void_p(t.data_ptr())
+    arr = (_lib.phz_lines * 1)(_lib.phz_lines(n_lines, p(dev["read_idx"]), p(dev["z32"]), p(dev["z8"]), n_reads, p(dev["qid"]), None, None, 0.0, 0, 0, 0, 0, p(dev["as16"])))
+    scores = as16[read_idx.long()]; scores = scores[scores != -32768].numpy().astype(np.int64)
+
+    def enqueue(m):
+        blk = torch.full((4,), -7.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        m.ctx.check(m.ctx.lib.phz_as_cutoff_enqueue(m.ctx.h, arr, 1, 37.0, p(blk)))
+        return blk
+    alone = Mapper(0)
+    blk = enqueue(alone)
+    alone.ctx.check(alone.ctx.lib.phz_ctx_sync(alone.ctx.h))
+    want = blk.cpu().numpy().copy()
+    assert want[1] == 1.0 and want[2] == 0.0 and want[3] == float(len(scores)) and want[0] == float(np.percentile(scores, 37.0))
+    m = Mapper(0)
+    pair = small_shards[0:2]
+    call, bufs, N = m.prepare_batch([s["dev"] for s in pair], [s["vpos"] for s in pair], 10, [len(s["want"][0]) + 8 for s in pair])
+    blk = enqueue(m)
+    m.ctx.check(call())                                                          # no phz_ctx_sync between the two
+    m.ctx.check(m.ctx.lib.phz_ctx_sync(m.ctx.h))
+    assert np.array_equal(blk.cpu().numpy(), want)
+    for i, s in enumerate(pair):
+        _same_lists(Calls(*[t[:int(N[i])] for t in bufs[i]]), s["want"])
+
+
+def test_repeated_and_changed_submissions(small_shards):
+    """What a ctx remembers of the last submission (the shard table and the overflow-area record on the device: a repeated submission uploads neither) must never
+    stand in for another submission's: A, A again, B (as many shards, other shards and buffers), A, A with half the room (PHZ_E_CAPACITY and the true counts),
+    A with full room."""
+    from phaser_amd import _lib
+    from phaser_amd.mapper import Calls, Mapper
+    m = Mapper(0)
+    A, B = small_shards[0:2], small_shards[2:4]
+    caps = [len(s["want"][0]) + 8 for s in A]
+    call, bufs, N = m.prepare_batch([s["dev"] for s in A], [s["vpos"] for s in A], 10, caps)
+    for rep in range(2):                                                         # the same arrays twice: the table of the second is already there
+        for b in bufs:
+            for t in b:
+                t.zero_()
+        torch.cuda.synchronize()
+        m.ctx.check(call())
+        for i, s in enumerate(A):
+            _same_lists(Calls(*[t[:int(N[i])] for t in bufs[i]]), s["want"])
+    for batch in (B, A):
+        st, got, n = _submit(m, batch)
+        assert st == _lib.PHZ_OK
+        for c, s in zip(got, batch):
+            _same_lists(c, s["want"])
+    half = [len(s["want"][0]) // 2 for s in A]
+    st, got, n = _submit(m, A, caps=half)
+    assert st == _lib.PHZ_E_CAPACITY and n == [len(s["want"][0]) for s in A]
+    for c, s, h in zip(got, A, half):
+        _same_lists(c, s["want"], n=h)                                          # the first `cap` calls are in place
+    st, got, n = _submit(m, A)
+    assert st == _lib.PHZ_OK
+    for c, s in zip(got, A):
+        _same_lists(c, s["want"])
+        _same_text(s, c.aux0.cpu().numpy(), c.aux1.cpu().numpy())
+
+
+def test_dead_shards_inside_a_batch(small_shards):
+    """Five shards, #0 without records, #2 without variants, #4 without either: no calls for those, and #1 / #3 -- the live shards, whose tiles are numbered
+    without the dead ones -- as the oracle has them and as each gives when submitted alone."""
+    from phaser_amd import _lib, soa
+    from phaser_amd.mapper import Mapper
+    m = Mapper(0)
+    empty = soa.pack_sam([]).to("cuda")
+    no_v = torch.zeros(0, dtype=torch.int32)
+    a, b = small_shards[1], small_shards[3]
+    batch = [{"dev": empty, "vpos": small_shards[0]["vpos"], "want": ([],) * 4}, a, {"dev": small_shards[2]["dev"], "vpos": no_v, "want": ([],) * 4}, b,
+             {"dev": empty, "vpos": no_v, "want": ([],) * 4}]
+    st, got, n = _submit(m, batch)
+    assert st == _lib.PHZ_OK and n[0] == n[2] == n[4] == 0 and n[1] == len(a["want"][0]) > 0 and n[3] == len(b["want"][0]) > 0
+    for k, s in ((1, a), (3, b)):
+        _same_lists(got[k], s["want"])
+        _, alone, _ = _submit(m, [s])
+        for f in ("read_idx", "var_idx", "code", "aux0", "aux1"):
+            assert torch.equal(getattr(alone[0], f), getattr(got[k], f)), (k, f)
+
+
+def test_host_space_callers_share_the_staging_pool(small_shards):
+    """phz_map_reads(PHZ_HOST) and phz_map_reads_general(PHZ_HOST) stage the caller's arrays through the same pool of the ctx: a small shard with the text planes,
+    a general call on another shard (SNPs as allele strings), a shard three times the first one's size without the planes, the first again -- every slot of the
+    pool changes owner and size in between."""
+    import ctypes as C
+    from phaser_amd import _lib, soa, synth
+    from phaser_amd.mapper import Mapper
+    m = Mapper(0)
+    p = lambda t: C.c_void_p(t.data_ptr())
+
+    def map_host(s, aux):
+        sh = s["host"]; cap = len(s["want"][0]) + 8
+        r = _lib.phz_reads(sh.n, int(sh.cigar.numel()), int(sh.seq2.numel()), p(sh.pos), p(sh.cigar_off), p(sh.cigar), p(sh.seq_off), p(sh.seq2), p(sh.qual))
+        vv = _lib.phz_variants(int(s["vpos"].numel()), p(s["vpos"]), None)
+        bufs = [torch.full((cap,), -1, dtype=torch.int32), torch.full((cap,), -1, dtype=torch.int32), torch.full((cap,), 255, dtype=torch.uint8)]
+        bufs += [torch.zeros(cap, dtype=torch.int32), torch.zeros(cap, dtype=torch.int32)] if aux else [None, None]
+        c = _lib.phz_calls(cap, *[None if t is None else p(t) for t in bufs])
+        n = C.c_int64(0)
+        m.ctx.check(m.ctx.lib.phz_map_reads(m.ctx.h, C.byref(r), C.byref(vv), 10, C.byref(c), C.byref(n), _lib.PHZ_HOST))
+        o_r, o_v, o_c, _ = s["want"]
+        assert n.value == len(o_r) > 0
+        assert np.array_equal(bufs[0][:n.value].numpy(), o_r) and np.array_equal(bufs[1][:n.value].numpy(), o_v) and np.array_equal(bufs[2][:n.value].numpy(), o_c)
+        if aux:
+            _same_text(s, bufs[3].numpy(), bufs[4].numpy())
+
+    small, big = small_shards[4], small_shards[3]
+    assert big["host"].n >= 3 * small["host"].n
+    map_host(small, aux=True)
+    # the general call: ~3,000 pairs over 400 SNPs, K_map's own list as the reference (the rule of test_general_kernel_agrees_with_snp_kernel)
+    v, gs, ge, w = synth.make_variants("chr1", 1, 2_000_000, 400, 31, n_genes=8)
+    rb = synth.make_reads(v, gs, ge, w, 3000, 32, n_rate=0.002)
+    rb = rb.select(synth.samtools_keep(rb, 255))
+    shard = soa.pack_readbatch(rb)
+    nv = len(v)
+    base = Mapper(0).map(shard.to("cuda"), v.pos, 10).cpu()
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    ab = np.zeros(2 * nv + 1, dtype=np.uint8); ab[0:2 * nv:2] = letters[v.ref.numpy()]; ab[1:2 * nv:2] = letters[v.alt.numpy()]
+    calls, pool = m.map_general(shard, v.pos.to(torch.int32), torch.ones(nv, dtype=torch.uint8), torch.arange(2 * nv + 1, dtype=torch.int32), torch.from_numpy(ab), 10,
+                                want_text=True)
+    assert base.n > 1000 and calls.n == base.n
+    assert torch.equal(calls.read_idx, base.read_idx) and torch.equal(calls.var_idx, base.var_idx)
+    bc = base.code.numpy().astype(np.int64); gc = calls.code.numpy().astype(np.int64); vi = base.var_idx.numpy()
+    single = bc < 4
+    want = np.where(bc == v.ref.numpy()[vi], 5, np.where(bc == v.alt.numpy()[vi], 6, bc))
+    assert np.array_equal(gc[single], want[single])
+    assert np.all(gc[~single] == 4) or np.all(np.isin(gc[~single], (4, 5, 6)))
+    toff = pool.call_off.numpy(); n4 = int((gc == 4).sum())
+    assert toff[0] == 0 and toff[-1] == len(pool.roff) and np.all(np.diff(toff) >= 0) and (np.diff(toff) > 0).sum() == n4
+    map_host(big, aux=False)
+    map_host(small, aux=True)
