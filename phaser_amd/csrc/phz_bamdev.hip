@@ -408,29 +408,29 @@ __global__ __launch_bounds__(256) void k_names_len(const uint32_t *off, const in
 
 }  // namespace
 
-// The two big buffers of a device BAM read are kept in the ctx between calls (the larger one wins a slot): take / give back
-static bool bam_keep_buffers() { const char *e = getenv("PHZ_BAM_KEEP_BUFFERS"); return !(e && atoi(e) == 0); }
-static void *bam_take(DevBuf *slot, size_t bytes, size_t *cap) {
+// The two big buffers of a device BAM read are kept in the ctx between calls (the larger one wins a slot): take / give back.  keep = BamKnobs::keep_buffers
+static void *bam_take(DevBuf *slot, size_t bytes, size_t *cap, bool keep) {
     if (slot && slot->p && slot->cap >= bytes) { void *p = slot->p; *cap = slot->cap; slot->p = nullptr; slot->cap = 0; return p; }
     // a fresh buffer gets ~3 % + 64 MB of head room: the BAMs of one sample differ by fractions of a percent, and a buffer cut to the byte sent every slightly larger
     // file to a new 15 GB hipMalloc (0.2-0.7 s each time on this runtime: profiles/r06/cli_4bam_full_before.txt, 'device buffers 684 ms' at the third of four BAMs)
     void *p = nullptr;
     const size_t roomy = bytes + bytes / 32 + ((size_t)64 << 20);
-    if (bam_keep_buffers() && hipMalloc(&p, roomy) == hipSuccess) { *cap = roomy; return p; }
+    if (keep && hipMalloc(&p, roomy) == hipSuccess) { *cap = roomy; return p; }
     (void)hipGetLastError();
     p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     *cap = bytes;
     return p;
 }
-static void bam_give_back(DevBuf *slot, void *p, size_t cap) {
+static void bam_give_back(DevBuf *slot, void *p, size_t cap, bool keep) {
     if (!p) return;
-    if (slot && bam_keep_buffers() && cap > slot->cap) { if (slot->p) (void)hipFree(slot->p); slot->p = p; slot->cap = cap; return; }
+    if (slot && keep && cap > slot->cap) { if (slot->p) (void)hipFree(slot->p); slot->p = p; slot->cap = cap; return; }
     (void)hipFree(p);
 }
 
 struct phz_bamdev {
     phz_ctx *ctx = nullptr;
+    bool keep_buffers = true;           // BamKnobs::keep_buffers of the call that opened the handle
     std::vector<std::pair<std::string, int32_t>> refs;
     void *d_stream = nullptr;           // inflated bytes of the needed members
     size_t d_stream_cap = 0;            // its size (the buffer goes back to the ctx's cache when the handle is closed)
@@ -444,355 +444,425 @@ struct phz_bamdev {
     std::vector<uint32_t> h_co, h_so, h_qo;     // values at the reference boundaries
     std::string err;
     ~phz_bamdev() {
-        if (d_stream) bam_give_back(ctx ? &ctx->bam_stream : nullptr, d_stream, d_stream_cap);
-        if (d_work) bam_give_back(ctx ? &ctx->bam_work : nullptr, d_work, d_work_cap);
+        if (d_stream) bam_give_back(ctx ? &ctx->bam_stream : nullptr, d_stream, d_stream_cap, keep_buffers);
+        if (d_work) bam_give_back(ctx ? &ctx->bam_work : nullptr, d_work, d_work_cap, keep_buffers);
     }
 };
 
-#define BD_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t _e = (call);                                                                           \
-        if (_e != hipSuccess) { phz_fail(ctx, PHZ_E_HIP, #call, _e); delete h; phz_bam_plan_release(&plan); return PHZ_E_HIP; } \
-    } while (0)
+namespace {
 
-extern "C" {
-
-int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names, int n_names, const phz_bam_filters *f, phz_bamdev **out) {
-    PhzEnter phz_guard_(ctx);
-    if (!ctx || !path || !f || !out) return PHZ_E_ARG;
-    *out = nullptr;
-    const bool timing = getenv("PHZ_TIMING") != nullptr;
-    auto t_lap = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[phz timing]     bam device: %-40s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_lap).count());
-        t_lap = now;
-    };
-    PhzBamPlan plan;
-    if (int st = phz_bam_plan_file(path, ref_names, n_names, &plan)) { phz_bam_plan_release(&plan); return st; }
-    lap("plan (member table, header, chromosome ranges)");
-    phz_bamdev *h = new phz_bamdev();
-    h->ctx = ctx;
-    h->refs = plan.refs;
-    const int n_ref = (int)plan.refs.size();
-    h->ref_begin.assign((size_t)n_ref + 1, 0);
-    h->h_co.assign((size_t)n_ref + 1, 0); h->h_so.assign((size_t)n_ref + 1, 0); h->h_qo.assign((size_t)n_ref + 1, 0);
-    if (plan.members.empty() || plan.pieces.empty()) { phz_bam_plan_release(&plan); *out = h; return PHZ_OK; }
-    if (hipSetDevice(ctx->device) != hipSuccess) { delete h; phz_bam_plan_release(&plan); return PHZ_E_HIP; }
-    hipStream_t sm = ctx->stream;
-    hipEvent_t e0 = ctx->ev0, e1 = ctx->ev1;
-    // ---- H2D of the compressed bytes: one contiguous file range per run of members; device member table with local offsets
-    std::vector<phz_bgzf_member> mem(plan.members.size());
-    uint64_t comp_bytes = 0, out_bytes = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> runs;          // file ranges [a, b)
-    std::vector<uint64_t> run_dev;                            // their offsets in the device buffer
-    {
-        uint64_t run_a = 0, run_b = 0;
-        for (size_t i = 0; i < plan.members.size(); i++) {
-            const auto &m = plan.members[i];
-            const uint64_t a = m.src, b = m.src + m.csize;
-            if (i == 0 || a > run_b + 65536) {
-                if (i) { runs.emplace_back(run_a, run_b); }
-                run_a = a; run_b = b;
-            } else run_b = b;
-        }
-        runs.emplace_back(run_a, run_b);
-        for (auto &r : runs) { run_dev.push_back(comp_bytes); comp_bytes += (r.second - r.first + 15) & ~(uint64_t)15; }
-    }
-    // inflated layout: the needed members back to back in file order (mem_dev_dst[i] = where member i's output starts)
-    std::vector<uint64_t> mem_dev_dst(plan.members.size());
-    {
-        size_t ri = 0;
-        for (size_t i = 0; i < plan.members.size(); i++) {
-            const auto &m = plan.members[i];
-            while (ri + 1 < runs.size() && m.src >= runs[ri].second) ri++;
-            mem[i].src = run_dev[ri] + (m.src - runs[ri].first);
-            mem[i].csize = m.csize; mem[i].isize = m.isize; mem[i].dst = out_bytes;
-            mem_dev_dst[i] = out_bytes;
-            out_bytes += m.isize;
-        }
-    }
-    auto dev_of = [&](uint64_t u) -> uint64_t {                // global inflated offset -> device stream offset
-        size_t lo = 0, hi = plan.members.size();
-        while (lo < hi) { const size_t m = (lo + hi) >> 1; if (plan.members[m].dst + plan.members[m].isize <= u) lo = m + 1; else hi = m; }
-        if (lo >= plan.members.size()) return out_bytes;       // u == end of the last member
-        return mem_dev_dst[lo] + (u - plan.members[lo].dst);
-    };
-    void *d_comp = nullptr, *d_mem = nullptr;
-    // Every allocation failure of the device path is PHZ_E_NOMEM (the caller then decodes the file on the host; earlier BAMs' shards stay
-    // resident, so HBM can legitimately be short here), and the runtime's sticky last-error is cleared so that the next kernel-launch check
-    // of this ctx does not report a stale out-of-memory.  PHZ_BAMDEV_FORCE_NOMEM=1 (tests) takes this exit without exhausting a GPU.
-    const bool force_nomem = getenv("PHZ_BAMDEV_FORCE_NOMEM") != nullptr;
-    size_t d_comp_cap = 0;
-    bool got = false;
-    for (int attempt = 0; attempt < 2 && !force_nomem && !got; attempt++) {
-        d_comp = bam_take(&ctx->bam_comp, comp_bytes + 64, &d_comp_cap);
-        if (d_comp && hipMalloc(&d_mem, mem.size() * sizeof(phz_bgzf_member) + mem.size() * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); d_mem = nullptr; }      // member table + the trailers' CRC32s behind it
-        if (d_comp && d_mem) h->d_stream = bam_take(&ctx->bam_stream, out_bytes + 64, &h->d_stream_cap);
-        got = d_comp && d_mem && h->d_stream;
-        if (!got) {             // short of memory: the kept buffers (too small for this file) go back to the runtime, then one more try
-            if (d_comp) { (void)hipFree(d_comp); d_comp = nullptr; }
-            if (d_mem) { (void)hipFree(d_mem); d_mem = nullptr; }
-            if (h->d_stream) { (void)hipFree(h->d_stream); h->d_stream = nullptr; }
-            if (ctx->bam_comp.p) { (void)hipFree(ctx->bam_comp.p); ctx->bam_comp = DevBuf(); }
-            if (ctx->bam_stream.p) { (void)hipFree(ctx->bam_stream.p); ctx->bam_stream = DevBuf(); }
-            if (ctx->bam_work.p) { (void)hipFree(ctx->bam_work.p); ctx->bam_work = DevBuf(); }
-        }
-    }
-    if (!got) {
-        (void)hipGetLastError();
-        delete h; phz_bam_plan_release(&plan); return phz_fail(ctx, PHZ_E_NOMEM, "device BAM buffers");
-    }
-    lap("device buffers");
-    // H2D and K_inflate overlapped: the members go over in chunks of ~1.3 GB of compressed bytes on a copy stream (the file is pageable
-    // memory, so every copy keeps this thread busy staging it), and each chunk's members are inflated on the compute stream as soon as
-    // its bytes have arrived -- the copy of chunk c+1 runs while chunk c inflates
-    auto t_h2d0 = std::chrono::steady_clock::now();
-    constexpr int NCOPY_MAX = 16;
-    int NCOPY = 8;                      // host threads (and streams) that read the file and send it over; PHZ_BAM_NCOPY = 1..16
-    { const char *e = getenv("PHZ_BAM_NCOPY"); if (e && atoi(e) >= 1 && atoi(e) <= NCOPY_MAX) NCOPY = atoi(e); }
-    hipStream_t cs[NCOPY_MAX];
-    for (int t = 0; t < NCOPY_MAX; t++) cs[t] = nullptr;
-    for (int t = 0; t < NCOPY; t++) if (hipStreamCreateWithFlags(&cs[t], hipStreamNonBlocking) != hipSuccess) cs[t] = nullptr;
-    if (phz_reserve(ctx, ctx->scalars, 64) != PHZ_OK || phz_reserve(ctx, ctx->scratch[SC_INFLATE_LENS], mem.size() * (size_t)phz_inflate_scratch_bytes_per_member()) != PHZ_OK) {
-        bam_give_back(&ctx->bam_comp, d_comp, d_comp_cap); (void)hipFree(d_mem); for (auto c : cs) if (c) (void)hipStreamDestroy(c);
-        (void)hipGetLastError();
-        delete h; phz_bam_plan_release(&plan); return PHZ_E_NOMEM;
-    }
-    int *d_status = (int *)ctx->scalars.p;
-    (void)hipMemsetAsync(d_status, 0, 4, sm);
-    (void)hipMemcpyAsync(d_mem, mem.data(), mem.size() * sizeof(phz_bgzf_member), hipMemcpyHostToDevice, sm);
-    // every member's output is checked against the CRC32 of its trailer after it has been inflated (htslib does, so the reference's `samtools view` stops on a
-    // damaged file that is still valid DEFLATE); PHZ_BAM_CRC=0 skips the check
-    std::vector<uint32_t> crcs(plan.members.size());
-    for (size_t i = 0; i < plan.members.size(); i++) crcs[i] = plan.members[i].crc;
-    uint32_t *d_crc = (uint32_t *)((char *)d_mem + mem.size() * sizeof(phz_bgzf_member));
-    bool crc_on = true;
-    { const char *e = getenv("PHZ_BAM_CRC"); if (e && atoi(e) == 0) crc_on = false; }
-    if (crc_on) (void)hipMemcpyAsync(d_crc, crcs.data(), crcs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, sm);
-    (void)hipEventRecord(e0, sm);
-    int st = PHZ_OK;
-    std::vector<hipEvent_t> evs;
-    // PHZ_BAM_REGISTER=1 (experiment, off by default): the mapped file's needed span registered with the runtime, DMA straight out of the page cache.  The
-    // copies then run at PCIe speed without host threads (212 against 241 ms for copy + K_inflate of a 3.8 GB BAM), but faulting the mapping's 930,000 pages
-    // into the page table costs 177 ms up front (profiles/r05/bam_device_sweep.txt): pread into page-locked staging never maps them and stays the default
-    bool reg_ok = false; void *reg_p = nullptr;
-    {
-        const char *e = getenv("PHZ_BAM_REGISTER");
-        if (e && atoi(e) == 1 && !runs.empty() && phz_bam_plan_map(&plan)) {
-            const uint64_t r0 = runs.front().first & ~(uint64_t)4095;
-            uint64_t r1 = (runs.back().second + 4095) & ~(uint64_t)4095;
-            if (r1 > ((plan.file_size + 4095) & ~(uint64_t)4095)) r1 = (plan.file_size + 4095) & ~(uint64_t)4095;
-            if (hipHostRegister((void *)(plan.file + r0), (size_t)(r1 - r0), hipHostRegisterDefault) == hipSuccess) { reg_ok = true; reg_p = (void *)(plan.file + r0); }
-            else (void)hipGetLastError();
-        }
-    }
-    lap("registration of the mapped file");
-    // page-locked staging: NCOPY threads x 2 buffers, kept in the ctx for the next BAM of the sample
-    constexpr uint64_t STAGE_BYTES = 8ull << 20;
-    const int fd = ::open(path, O_RDONLY);
-    bool stage_ok = !reg_ok && fd >= 0 && phz_reserve_host(ctx, ctx->h_bam_stage, (size_t)NCOPY * 2 * STAGE_BYTES) == PHZ_OK;
-    if (!stage_ok && !reg_ok) {
-        (void)hipGetLastError();
-        if (!phz_bam_plan_map(&plan)) {                    // no page-locked staging and no mapping either
-            if (fd >= 0) ::close(fd);
-            bam_give_back(&ctx->bam_comp, d_comp, d_comp_cap); (void)hipFree(d_mem); for (auto c : cs) if (c) (void)hipStreamDestroy(c);
-            delete h; phz_bam_plan_release(&plan); return PHZ_E_NOMEM;
-        }
-    }
-    char *stage = (char *)ctx->h_bam_stage.p;
-    hipEvent_t stage_ev[NCOPY_MAX * 2];
-    for (auto &e : stage_ev) e = nullptr;
-    for (int t = 0; t < NCOPY * 2; t++) if (stage_ok && hipEventCreateWithFlags(&stage_ev[t], hipEventDisableTiming) != hipSuccess) stage_ev[t] = nullptr;
-    int n_is = 1, n_launch = 0;
+// The switches of one phz_bamdev_open, read once at its top (tests change them between calls on one ctx): nothing below this struct calls getenv
+struct BamKnobs {
+    static constexpr int NCOPY_MAX = 16;
+    bool timing;                 // PHZ_TIMING: the [phz timing] lines
+    bool force_nomem;            // PHZ_BAMDEV_FORCE_NOMEM=1 (tests): the out-of-memory exit without exhausting a GPU
+    bool crc;                    // PHZ_BAM_CRC=0 skips the check of every member's output against the CRC32 of its trailer
+    bool keep_buffers;           // PHZ_BAM_KEEP_BUFFERS=0 turns the ctx's cache of the big buffers off
+    bool many_queues;            // GPU_MAX_HW_QUEUES >= 16 (PHZ_HW_QUEUES_LATE: the variable was set after the runtime had started, so it does not count)
+    int ncopy;                   // PHZ_BAM_NCOPY = 1..16: host threads (and streams) that read the file and send it over
+    int inflate_streams;         // PHZ_BAM_INFLATE_STREAMS = 1..8
+    uint64_t chunk_bytes;        // PHZ_BAM_CHUNK_MB: compressed bytes per K_inflate launch
+    uint64_t limit;              // PHZ_BAMDEV_LIMIT: the 32-bit limit of a call's byte sums (tests lower it to exercise the caller's split)
+    uint64_t slice_min;          // PHZ_BAM_SLICE_MIN_KB (65536): a chunk of at least this many bytes goes over in ncopy slices
+    uint64_t stage_bytes;        // PHZ_BAM_STAGE_KB (8192): one page-locked staging buffer; a multiple of 4 KB, at least 4.  Tests lower these two so that a small
+                                 // file goes through the threaded staging copy and reuses its buffers
+    static long long num(const char *name, long long dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
     // K_inflate launches of consecutive chunks overlap only when their streams sit on different HARDWARE queues: the runtime spreads a process's streams over
     // GPU_MAX_HW_QUEUES of them (default 4) and this call alone has eight copy streams -- a copy stream that shares the queue of a running K_inflate waits
     // behind it, which serialised everything (profiles/r05/bam_device_sweep_streams.txt: 12 chunks on 4 streams 0.69 s with 4 queues, 0.30 s with 16).  With
     // >= 16 queues (the package asks for them before the runtime starts, phaser_amd/__init__.py): 3 streams x 1,280 MB chunks, file -> shards 0.24 s; a host
     // application that keeps the runtime's default gets ONE launch per 4 GB (0.27 s; 0.32 s with the old 1,280 MB chunks on one stream).
-    bool many_queues = false;
-    { const char *q = getenv("GPU_MAX_HW_QUEUES"); many_queues = q && atoi(q) >= 16 && getenv("PHZ_HW_QUEUES_LATE") == nullptr; }      // (LATE: the variable was set after the runtime had started)
-    if (many_queues) n_is = 3;
-    { const char *e = getenv("PHZ_BAM_INFLATE_STREAMS"); if (e && atoi(e) >= 1 && atoi(e) <= 8) n_is = atoi(e); }
-    std::vector<hipStream_t> is((size_t)n_is, nullptr);
-    if (n_is > 1) {
-        (void)hipStreamSynchronize(sm);                  // the member table and the cleared status word are on the device before any other stream reads them
-        bool all = true;
-        for (size_t t = 0; t < is.size(); t++) if (hipStreamCreateWithFlags(&is[t], hipStreamNonBlocking) != hipSuccess) { is[t] = nullptr; all = false; }
-        if (!all) {          // one stream could not be made: every stream that was goes away again, the chunks take the ctx stream
-            for (size_t t = 0; t < is.size(); t++) if (is[t]) { (void)hipStreamDestroy(is[t]); is[t] = nullptr; }
-            n_is = 1;
-        }
+    // A launch lasts as long as its slowest member (60-100 ms) however few it holds, and the chip holds 262,000 members at once: big chunks.
+    BamKnobs() {
+        timing = getenv("PHZ_TIMING") != nullptr;
+        force_nomem = getenv("PHZ_BAMDEV_FORCE_NOMEM") != nullptr;
+        crc = num("PHZ_BAM_CRC", 1) != 0;
+        keep_buffers = num("PHZ_BAM_KEEP_BUFFERS", 1) != 0;
+        many_queues = num("GPU_MAX_HW_QUEUES", 0) >= 16 && getenv("PHZ_HW_QUEUES_LATE") == nullptr;
+        const long long nc = num("PHZ_BAM_NCOPY", 8), ns = num("PHZ_BAM_INFLATE_STREAMS", 0), mb = num("PHZ_BAM_CHUNK_MB", 0);
+        ncopy = nc >= 1 && nc <= NCOPY_MAX ? (int)nc : 8;
+        inflate_streams = ns >= 1 && ns <= 8 ? (int)ns : (many_queues ? 3 : 1);
+        chunk_bytes = (uint64_t)(mb > 0 ? mb : (many_queues ? 1280 : 4096)) << 20;
+        limit = (uint64_t)num("PHZ_BAMDEV_LIMIT", (1ll << 32) - 16);
+        const long long sl = num("PHZ_BAM_SLICE_MIN_KB", 65536), sk = num("PHZ_BAM_STAGE_KB", 8192);
+        slice_min = (uint64_t)(sl > 0 ? sl : 65536) << 10;
+        stage_bytes = (uint64_t)((sk < 4 ? 4 : sk) & ~3ll) << 10;
     }
-    {
-        // a launch lasts as long as its slowest member (60-100 ms) however few it holds, and the chip holds 262,000 members at once: big chunks (PHZ_BAM_CHUNK_MB)
-        const char *ch_env = getenv("PHZ_BAM_CHUNK_MB");
-        const uint64_t CH = (ch_env && atoll(ch_env) > 0 ? (uint64_t)atoll(ch_env) : (many_queues ? 1280ull : 4096ull)) << 20;
-        size_t ri = 0, i0 = 0;
-        while (i0 < plan.members.size() && st == PHZ_OK) {
-            while (ri + 1 < runs.size() && plan.members[i0].src >= runs[ri].second) ri++;
+};
+
+// ---- What the plan and the chunk size decide, computed on the host before anything touches the device.
+// Compressed side: one contiguous file range per run of members (a gap of more than 64 KB starts a new run), the runs back to back in d_comp, 16-byte aligned.
+// Inflated side: the needed members back to back in file order (mem[i].dst = where member i's output starts in the device stream).
+struct BamChunk { size_t first, count; uint64_t a, b; size_t run; };      // members [first, first + count) of one K_inflate launch, their file range [a, b), its run
+struct BamLayout {
+    static constexpr uint64_t SEG = 256u << 10;
+    const PhzBamPlan *plan = nullptr;
+    std::vector<std::pair<uint64_t, uint64_t>> runs;          // file ranges [a, b)
+    std::vector<uint64_t> run_dev;                            // their offsets in the device buffer
+    std::vector<phz_bgzf_member> mem;                         // device member table: src = offset in d_comp, dst = offset in the inflated stream
+    std::vector<uint32_t> crcs;                               // the trailers' CRC32s, member order
+    uint64_t comp_bytes = 0, out_bytes = 0;
+    std::vector<BamChunk> chunks;
+    std::vector<Seg> segs;                                    // the inflated stream's pieces cut every SEG bytes (exact = the piece's own start: a known boundary)
+
+    void build(const PhzBamPlan &p, uint64_t chunk_bytes) {
+        plan = &p;
+        const auto &M = p.members;
+        uint64_t run_a = 0, run_b = 0;
+        for (size_t i = 0; i < M.size(); i++) {
+            const uint64_t a = M[i].src, b = M[i].src + M[i].csize;
+            if (i == 0 || a > run_b + 65536) {
+                if (i) runs.emplace_back(run_a, run_b);
+                run_a = a; run_b = b;
+            } else run_b = b;
+        }
+        runs.emplace_back(run_a, run_b);
+        for (auto &r : runs) { run_dev.push_back(comp_bytes); comp_bytes += (r.second - r.first + 15) & ~(uint64_t)15; }
+        mem.resize(M.size()); crcs.resize(M.size());
+        for (size_t i = 0, ri = 0; i < M.size(); i++) {
+            while (ri + 1 < runs.size() && M[i].src >= runs[ri].second) ri++;
+            mem[i].src = run_dev[ri] + (M[i].src - runs[ri].first);
+            mem[i].csize = M[i].csize; mem[i].isize = M[i].isize; mem[i].dst = out_bytes;
+            crcs[i] = M[i].crc;
+            out_bytes += M[i].isize;
+        }
+        // chunks: members of one run, up to chunk_bytes of file (a chunk's first member may reach twice that)
+        for (size_t i0 = 0, ri = 0; i0 < M.size();) {
+            while (ri + 1 < runs.size() && M[i0].src >= runs[ri].second) ri++;
             size_t i1 = i0;
-            const uint64_t a = plan.members[i0].src;
+            const uint64_t a = M[i0].src;
             uint64_t bnd = a;
-            while (i1 < plan.members.size() && plan.members[i1].src < runs[ri].second && plan.members[i1].src + plan.members[i1].csize - a <= CH + (i1 == i0 ? CH : 0)) {
-                bnd = plan.members[i1].src + plan.members[i1].csize; i1++;
+            while (i1 < M.size() && M[i1].src < runs[ri].second && M[i1].src + M[i1].csize - a <= chunk_bytes + (i1 == i0 ? chunk_bytes : 0)) {
+                bnd = M[i1].src + M[i1].csize; i1++;
             }
-            if (i1 == i0) { bnd = plan.members[i0].src + plan.members[i0].csize; i1 = i0 + 1; }
-            // The chunk goes over in NCOPY slices, each read by its own host thread with pread() into page-locked staging buffers of its own
-            // (two per thread, in turn) and sent on its own stream.  Copying out of the mapped file instead -- pageable memory, staged by the
-            // runtime at ~13 GB/s per thread -- also populated a page-table entry for every page of the file: 0.16 s of munmap afterwards for
-            // a 3.8 GB BAM, on top of 0.34 s for the copy.
-            {
-                char *dst = (char *)d_comp + run_dev[ri] + (a - runs[ri].first);
-                const uint64_t len = bnd - a;
-                if (reg_ok) {
-                    // the mapped file is registered with the runtime: the DMA engines read the page cache directly, four slices on four streams
-                    // (tools/h2d_probe.py on this box: 56 GB/s out of a registered mapping; pread into page-locked staging + copy reached 13 GB/s
-                    // here while K_inflate ran -- 52 GB/s alone --, and kept eight host threads busy)
-                    const int nsl4 = len >= (64u << 20) ? 4 : 1;
-                    bool okc = true;
-                    for (int t = 0; t < nsl4; t++) {
-                        const uint64_t lo = (len * (uint64_t)t / (uint64_t)nsl4) & ~(uint64_t)4095, hi = t + 1 == nsl4 ? len : ((len * (uint64_t)(t + 1) / (uint64_t)nsl4) & ~(uint64_t)4095);
-                        if (hi > lo && hipMemcpyAsync(dst + lo, plan.file + a + lo, hi - lo, hipMemcpyHostToDevice, cs[t] ? cs[t] : sm) != hipSuccess) okc = false;
-                    }
-                    for (int t = 0; t < nsl4; t++) if (hipStreamSynchronize(cs[t] ? cs[t] : sm) != hipSuccess) okc = false;
-                    if (!okc) { st = PHZ_E_HIP; break; }
-                } else {
-                const int nsl = (cs[0] && stage_ok && len >= (64u << 20)) ? NCOPY : 1;
-                std::vector<std::thread> th;
-                std::vector<int> thst((size_t)nsl, PHZ_OK);
-                for (int t = 0; t < nsl; t++)
-                    th.emplace_back([&, t] {
-                        (void)hipSetDevice(ctx->device);
-                        const uint64_t lo = (len * (uint64_t)t / (uint64_t)nsl) & ~(uint64_t)4095, hi = t + 1 == nsl ? len : ((len * (uint64_t)(t + 1) / (uint64_t)nsl) & ~(uint64_t)4095);
-                        hipStream_t s2 = cs[t] ? cs[t] : sm;
-                        if (!stage_ok) {                                   // no staging memory: the mapped file, as before
-                            if (hipMemcpyAsync(dst + lo, plan.file + a + lo, hi - lo, hipMemcpyHostToDevice, s2) != hipSuccess) thst[(size_t)t] = PHZ_E_HIP;
-                            (void)hipStreamSynchronize(s2);
-                            return;
-                        }
-                        int which = 0;
-                        for (uint64_t o = lo; o < hi; o += STAGE_BYTES, which ^= 1) {
-                            const uint64_t m = hi - o < STAGE_BYTES ? hi - o : STAGE_BYTES;
-                            char *sb = stage + ((size_t)t * 2 + (size_t)which) * STAGE_BYTES;
-                            if (stage_ev[(size_t)t * 2 + (size_t)which] && hipEventSynchronize(stage_ev[(size_t)t * 2 + (size_t)which]) != hipSuccess) { thst[(size_t)t] = PHZ_E_HIP; return; }
-                            uint64_t got = 0;
-                            while (got < m) {
-                                const ssize_t r = pread(fd, sb + got, (size_t)(m - got), (off_t)(a + o + got));
-                                if (r <= 0) { thst[(size_t)t] = PHZ_E_ARG; return; }
-                                got += (uint64_t)r;
-                            }
-                            if (hipMemcpyAsync(dst + o, sb, m, hipMemcpyHostToDevice, s2) != hipSuccess) { thst[(size_t)t] = PHZ_E_HIP; return; }
-                            if (stage_ev[(size_t)t * 2 + (size_t)which]) (void)hipEventRecord(stage_ev[(size_t)t * 2 + (size_t)which], s2);
-                            else (void)hipStreamSynchronize(s2);
-                        }
-                        (void)hipStreamSynchronize(s2);                   // the slice is on the device (and the staging buffers are free again)
-                    });
-                for (auto &x : th) x.join();
-                for (int v : thst) if (v != PHZ_OK && st == PHZ_OK) st = v;
-                if (st != PHZ_OK) break;
-                }
-            }
-            // the K_inflate launches take turns on n_is streams: a chunk's members start while the previous launches are still running (see above)
-            hipStream_t si = n_is > 1 ? is[(size_t)(n_launch % n_is)] : sm;
-            st = phz_inflate_launch(ctx, (const uint8_t *)d_comp, (const phz_bgzf_member *)d_mem, (int64_t)i0, (int64_t)(i1 - i0), (uint8_t *)h->d_stream,
-                                    (uint8_t *)ctx->scratch[SC_INFLATE_LENS].p, d_status, si);
-            if (st == PHZ_OK && crc_on) st = phz_crc_launch(ctx, (const phz_bgzf_member *)d_mem, (int64_t)i0, (int64_t)(i1 - i0), (const uint8_t *)h->d_stream, d_crc, d_status, si);
-            n_launch++;
+            if (i1 == i0) { bnd = M[i0].src + M[i0].csize; i1 = i0 + 1; }
+            chunks.push_back({i0, i1 - i0, a, bnd, ri});
             i0 = i1;
         }
+        for (size_t pi = 0; pi < p.pieces.size(); pi++) {
+            const uint64_t a = dev_of(p.pieces[pi].first), b = a + (p.pieces[pi].second - p.pieces[pi].first);
+            for (uint64_t g = a; g < b; g += SEG) segs.push_back({g, b, g == a ? 1u : 0u, (uint32_t)pi});
+        }
     }
-    for (int t = 0; t < n_is; t++) if (is[(size_t)t]) { (void)hipStreamSynchronize(is[(size_t)t]); (void)hipStreamDestroy(is[(size_t)t]); }
-    (void)hipEventRecord(e1, sm);
-    int bad = 0;
-    (void)hipMemcpyAsync(&bad, d_status, 4, hipMemcpyDeviceToHost, sm);
-    (void)hipStreamSynchronize(sm);
-    for (auto c : cs) if (c) { (void)hipStreamSynchronize(c); (void)hipStreamDestroy(c); }
-    for (auto ev : evs) (void)hipEventDestroy(ev);
-    for (auto e : stage_ev) if (e) (void)hipEventDestroy(e);
-    if (reg_p) (void)hipHostUnregister(reg_p);
-    if (fd >= 0) ::close(fd);
-    const double h2d_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_h2d0).count();
-    float inflate_ms = 0;
-    (void)hipEventElapsedTime(&inflate_ms, e0, e1);
-    ctx->last_ms[PHZ_T_INFLATE] = inflate_ms; ctx->total_ms[PHZ_T_INFLATE] += inflate_ms; ctx->launches[PHZ_T_INFLATE]++;
-    bam_give_back(&ctx->bam_comp, d_comp, d_comp_cap); (void)hipFree(d_mem);
-    if (st != PHZ_OK || bad) { delete h; phz_bam_plan_release(&plan); if (st == PHZ_OK) ctx->err = bad == 7 ? "a BGZF member does not give the CRC32 of its trailer" : "a BGZF member is not valid DEFLATE"; return st != PHZ_OK ? st : PHZ_E_UNSUPPORTED; }
-    lap("H2D + K_inflate (+ free of the compressed copy)");
-    phz_bam_plan_release(&plan);         // closes the file (nothing was mapped unless a fallback copied out of a mapping)
-    lap("release of the plan");
-    // ---- segments
-    const uint64_t SEG = 256u << 10;
-    std::vector<Seg> segs;
-    for (size_t pi = 0; pi < plan.pieces.size(); pi++) {
-        const uint64_t a = dev_of(plan.pieces[pi].first), b = a + (plan.pieces[pi].second - plan.pieces[pi].first);
-        for (uint64_t g = a; g < b; g += SEG) segs.push_back({g, b, g == a ? 1u : 0u, (uint32_t)pi});
+    uint64_t dev_of(uint64_t u) const {                       // global inflated offset -> device stream offset
+        const auto &M = plan->members;
+        size_t lo = 0, hi = M.size();
+        while (lo < hi) { const size_t m = (lo + hi) >> 1; if (M[m].dst + M[m].isize <= u) lo = m + 1; else hi = m; }
+        if (lo >= M.size()) return out_bytes;                 // u == end of the last member
+        return mem[lo].dst + (u - M[lo].dst);
     }
-    const int64_t nseg = (int64_t)segs.size();
-    if (nseg == 0) { *out = h; return PHZ_OK; }
-    void *d_seg = nullptr;
-    const size_t seg_bytes = ((size_t)nseg * sizeof(Seg) + 255) & ~(size_t)255, start_bytes = ((size_t)(nseg + 1) * 8 + 255) & ~(size_t)255,
-                 so_bytes = ((size_t)nseg * sizeof(SegOut) + 255) & ~(size_t)255, kept_bytes = ((size_t)(nseg + 2) * 4 + 255) & ~(size_t)255;
-    const size_t mask_bytes = ((size_t)n_ref + 255) & ~(size_t)255;
-    if (hipMalloc(&d_seg, seg_bytes + start_bytes + so_bytes + 2 * kept_bytes + mask_bytes) != hipSuccess) { (void)hipGetLastError(); delete h; return phz_fail(ctx, PHZ_E_NOMEM, "device BAM segments"); }
-    Seg *dsegs = (Seg *)d_seg;
-    uint64_t *dstart = (uint64_t *)((char *)d_seg + seg_bytes);
-    SegOut *dso = (SegOut *)((char *)dstart + start_bytes);
-    uint32_t *dkept = (uint32_t *)((char *)dso + so_bytes), *dkbase = (uint32_t *)((char *)dkept + kept_bytes);
-    uint8_t *dmask = (uint8_t *)((char *)dkbase + kept_bytes);
-    std::vector<uint8_t> mask((size_t)n_ref, ref_names ? 0 : 1);
-    if (ref_names) for (int i = 0; i < n_ref; i++) for (int k = 0; k < n_names; k++) if (h->refs[(size_t)i].first == ref_names[k]) mask[(size_t)i] = 1;
-    auto fail = [&](int code, const char *what) { (void)hipFree(d_seg); if (what) ctx->err = what; delete h; return code; };
-    if (hipMemcpyAsync(dsegs, segs.data(), (size_t)nseg * sizeof(Seg), hipMemcpyHostToDevice, sm) != hipSuccess ||
-        hipMemcpyAsync(dmask, mask.data(), (size_t)n_ref, hipMemcpyHostToDevice, sm) != hipSuccess) return fail(PHZ_E_HIP, "hipMemcpyAsync");
-    Filters F; F.min_mapq = f->min_mapq; F.flag_required = f->flag_required; F.flag_forbidden = f->flag_forbidden; F.isize_cutoff = f->isize_cutoff;
-    F.ref_mask = dmask; F.n_ref = n_ref;
-    const uint8_t *d = (const uint8_t *)h->d_stream;
-    (void)hipEventRecord(e0, sm);
-    const unsigned gseg = (unsigned)((nseg + 63) / 64);
-    hipLaunchKernelGGL(k_seg_start, dim3(gseg), dim3(64), 0, sm, d, (const Seg *)dsegs, nseg, n_ref, dstart);
-    KeptOut none{};
-    std::vector<SegOut> hso((size_t)nseg);
-    uint32_t total_kept = 0;
-    // The counting hop, repeated while a guessed boundary turns out to be a fake (a byte pattern inside a record that passes the
-    // plausibility chain): segment k's chain is the truth when its own start is, so where it ARRIVES becomes the start of segment
-    // k + 1, and the hop runs again.  Every boundary is verified in the end, or the file goes to the host path.
-    for (int pass = 0;; pass++) {
-        hipLaunchKernelGGL(k_hop<0>, dim3(gseg), dim3(64), 0, sm, d, (const Seg *)dsegs, nseg, (const uint64_t *)dstart, F, dso, (const uint32_t *)nullptr, none);
-        if (hipMemcpyAsync(hso.data(), dso, (size_t)nseg * sizeof(SegOut), hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
-            return fail(PHZ_E_HIP, "segment read-back");
-        int repaired = 0;
-        bool prev_clean = true;
-        for (int64_t k = 0; k < nseg; k++) {
-            const SegOut &o = hso[(size_t)k];
-            const bool last_of_piece = !(k + 1 < nseg && segs[(size_t)k + 1].piece == segs[(size_t)k].piece);
-            if ((o.flags & 1) && prev_clean) return fail(PHZ_E_ARG, "truncated or corrupt BAM record");
-            if ((o.flags & 2) && prev_clean) {
-                if (last_of_piece) return fail(PHZ_E_ARG, "truncated or corrupt BAM record");      // ran past the end of the piece
-                if (hipMemcpyAsync(dstart + k + 1, &hso[(size_t)k].end_pos, 8, hipMemcpyHostToDevice, sm) != hipSuccess) return fail(PHZ_E_HIP, "boundary repair");
-                repaired++;
+    uint64_t comp_at(const BamChunk &c) const { return run_dev[c.run] + (c.a - runs[c.run].first); }      // where the chunk's bytes go in d_comp
+};
+
+// ---- the two allocations the driver carves into parts, every part 256-byte aligned: byte offsets computed once, typed pointers handed out
+static size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+template <class T> static T *bam_part(void *p, size_t off) { return (T *)((char *)p + off); }
+// BamOpen::d_seg: [Seg x nseg][start x (nseg + 1)][SegOut x nseg][kept x (nseg + 2)][kbase x (nseg + 2)][reference mask x n_ref]
+struct SegCarve {
+    size_t off_start = 0, off_so = 0, off_kept = 0, off_kbase = 0, off_mask = 0, bytes = 0;
+    SegCarve() {}
+    SegCarve(int64_t nseg, int n_ref) {
+        off_start = al256((size_t)nseg * sizeof(Seg)); off_so = off_start + al256((size_t)(nseg + 1) * 8); off_kept = off_so + al256((size_t)nseg * sizeof(SegOut));
+        off_kbase = off_kept + al256((size_t)(nseg + 2) * 4); off_mask = off_kbase + al256((size_t)(nseg + 2) * 4); bytes = off_mask + al256((size_t)n_ref);
+    }
+    Seg *segs(void *p) const { return bam_part<Seg>(p, 0); }
+    uint64_t *start(void *p) const { return bam_part<uint64_t>(p, off_start); }
+    SegOut *so(void *p) const { return bam_part<SegOut>(p, off_so); }
+    uint32_t *kept(void *p) const { return bam_part<uint32_t>(p, off_kept); }
+    uint32_t *kbase(void *p) const { return bam_part<uint32_t>(p, off_kbase); }
+    uint8_t *mask(void *p) const { return bam_part<uint8_t>(p, off_mask); }
+};
+// phz_bamdev::d_work: [KeptOut.off x n][KeptOut.ref, nops, sq, nb, lqn x (n + 1)][co, so, qo x (n + 1)][ref_begin x (n_ref + 2)], n = kept records (at least 1)
+struct KeptCarve {
+    size_t a8, a4, rb;
+    KeptCarve(int64_t nk, int n_ref) : a8(al256((size_t)(nk ? nk : 1) * 8)), a4(al256(((size_t)(nk ? nk : 1) + 1) * 4)), rb(al256((size_t)(n_ref + 2) * 8)) {}
+    size_t bytes() const { return a8 + 8 * a4 + rb; }
+    template <class T> T *word(void *p, int k) const { return bam_part<T>(p, a8 + (size_t)k * a4); }          // the k-th of the eight 4-byte arrays
+    void point(phz_bamdev *h) const {
+        void *p = h->d_work;
+        h->K.off = bam_part<uint64_t>(p, 0);
+        h->K.ref = word<int32_t>(p, 0); h->K.nops = word<uint32_t>(p, 1); h->K.sq = word<uint32_t>(p, 2); h->K.nb = word<uint32_t>(p, 3); h->K.lqn = word<uint32_t>(p, 4);
+        h->co = word<uint32_t>(p, 5); h->so = word<uint32_t>(p, 6); h->qo = word<uint32_t>(p, 7);
+        h->d_ref_begin = bam_part<int64_t>(p, a8 + 8 * a4);
+    }
+};
+
+// What one phz_bamdev_open knows and OWNS: the plan, the handle until success hands it to the caller, the compressed copy and the member table, the copy and
+// inflate streams, the staging events, the file descriptor, the segment allocation.  Its functions are the stages of the call in stream order (run()).
+// THE RULE of its clean-up: no buffer goes back to the ctx cache or to the runtime while work that touches it can still be queued.  So the destructor, which
+// every exit goes through, releases in ONE order: the inflate streams, then the copy streams (each waited for, then destroyed), the events, the file
+// descriptor; on a failing exit a wait for the ctx stream (the hop or a scan may still be queued on the handle's buffers); only then d_comp back to the cache,
+// d_mem and d_seg freed, the plan released and the handle, unless it was handed over, deleted (its two buffers return to the cache).  A successful call has
+// released each of these at its old place in the sequence already (the drop_* functions release once), and pays nothing here.
+struct BamOpen {
+    using Clock = std::chrono::steady_clock;
+    phz_ctx *const ctx; const char *const path; const char *const *const ref_names; const int n_names; const phz_bam_filters *const f; phz_bamdev **const out;
+    const BamKnobs knobs;
+    const hipStream_t sm; const hipEvent_t e0, e1;
+    int status = PHZ_OK;
+    // owned (see above)
+    PhzBamPlan plan; phz_bamdev *h = nullptr;
+    void *d_comp = nullptr; size_t d_comp_cap = 0; void *d_mem = nullptr, *d_seg = nullptr;
+    hipStream_t cs[BamKnobs::NCOPY_MAX] = {}; std::vector<hipStream_t> is; hipEvent_t stage_ev[BamKnobs::NCOPY_MAX * 2] = {}; int fd = -1;
+    // what a stage leaves for the next ones
+    BamLayout L; int n_ref = 0;
+    int *d_status = nullptr; bool stage_ok = false; int n_is = 1, n_launch = 0, n_slices = 0; long long n_rounds = 0;
+    SegCarve seg; int64_t nseg = 0; unsigned gseg = 0; Filters F{}; std::vector<uint8_t> mask; std::vector<SegOut> hso; uint32_t total_kept = 0;
+    Clock::time_point t_lap = Clock::now(), t_h2d0; double h2d_ms = 0; float inflate_ms = 0;
+
+    BamOpen(phz_ctx *c, const char *path_, const char *const *ref_names_, int n_names_, const phz_bam_filters *f_, phz_bamdev **out_)
+        : ctx(c), path(path_), ref_names(ref_names_), n_names(n_names_), f(f_), out(out_), sm(c->stream), e0(c->ev0), e1(c->ev1) {}
+    ~BamOpen() {
+        drop_inflate_streams(); drop_copy_streams(); drop_staging();
+        if (status != PHZ_OK) (void)hipStreamSynchronize(sm);
+        drop_compressed(); drop_segments();
+        phz_bam_plan_release(&plan);
+        delete h;
+        // Every allocation failure of the device path is PHZ_E_NOMEM (the caller then decodes the file on the host; earlier BAMs' shards stay resident, so HBM can
+        // legitimately be short here), and the runtime's sticky last-error is cleared so that the next kernel-launch check of this ctx does not report a stale
+        // out-of-memory
+        if (status == PHZ_E_NOMEM) (void)hipGetLastError();
+    }
+    void drop_inflate_streams() { for (auto &s : is) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); s = nullptr; } }
+    void drop_copy_streams() { for (auto &c : cs) if (c) { (void)hipStreamSynchronize(c); (void)hipStreamDestroy(c); c = nullptr; } }
+    void drop_staging() { for (auto &e : stage_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } if (fd >= 0) { ::close(fd); fd = -1; } }
+    void drop_compressed() { bam_give_back(&ctx->bam_comp, d_comp, d_comp_cap, knobs.keep_buffers); d_comp = nullptr; if (d_mem) { (void)hipFree(d_mem); d_mem = nullptr; } }
+    void drop_segments() { if (d_seg) { (void)hipFree(d_seg); d_seg = nullptr; } }
+
+    int fail(int code, const char *what) { if (what) ctx->err = what; status = code; return code; }      // every failing exit: the destructor does the rest
+    int hand_over() { *out = h; h = nullptr; return PHZ_OK; }
+    void lap(const char *what) {
+        if (!knobs.timing) return;
+        const auto now = Clock::now();
+        fprintf(stderr, "[phz timing]     bam device: %-40s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_lap).count());
+        t_lap = now;
+    }
+
+    int run() {
+        if (int st = make_plan()) return st;
+        if (plan.members.empty() || plan.pieces.empty()) return hand_over();         // no wanted record in the file: a handle without records
+        if (hipSetDevice(ctx->device) != hipSuccess) return fail(PHZ_E_HIP, nullptr);
+        L.build(plan, knobs.chunk_bytes);
+        if (int st = device_buffers()) return st;
+        if (int st = upload_tables()) return st;
+        if (int st = copy_and_inflate()) return st;
+        if (L.segs.empty()) return hand_over();
+        if (int st = segments()) return st;
+        if (int st = counting_hop()) return st;
+        if (int st = host_checks()) return st;
+        if (int st = kept_list()) return st;
+        if (int st = read_backs()) return st;
+        return hand_over();
+    }
+
+    // ---- 1. plan (host: member table, header, chromosome ranges) and the handle
+    int make_plan() {
+        if (int st = phz_bam_plan_file(path, ref_names, n_names, &plan)) return fail(st, nullptr);
+        lap("plan (member table, header, chromosome ranges)");
+        h = new phz_bamdev();
+        h->ctx = ctx; h->keep_buffers = knobs.keep_buffers;
+        h->refs = plan.refs;
+        n_ref = (int)plan.refs.size();
+        h->ref_begin.assign((size_t)n_ref + 1, 0);
+        h->h_co.assign((size_t)n_ref + 1, 0); h->h_so.assign((size_t)n_ref + 1, 0); h->h_qo.assign((size_t)n_ref + 1, 0);
+        return PHZ_OK;
+    }
+    // ---- 3. device buffers: compressed copy, member table + the trailers' CRC32s behind it, inflated stream.  Short of memory: the kept buffers (too small for
+    // this file) go back to the runtime, then one more try
+    int device_buffers() {
+        bool got = false;
+        for (int attempt = 0; attempt < 2 && !knobs.force_nomem && !got; attempt++) {
+            d_comp = bam_take(&ctx->bam_comp, L.comp_bytes + 64, &d_comp_cap, knobs.keep_buffers);
+            if (d_comp && hipMalloc(&d_mem, L.mem.size() * sizeof(phz_bgzf_member) + L.mem.size() * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); d_mem = nullptr; }
+            if (d_comp && d_mem) h->d_stream = bam_take(&ctx->bam_stream, L.out_bytes + 64, &h->d_stream_cap, knobs.keep_buffers);
+            got = d_comp && d_mem && h->d_stream;
+            if (!got) {
+                if (d_comp) { (void)hipFree(d_comp); d_comp = nullptr; }
+                if (d_mem) { (void)hipFree(d_mem); d_mem = nullptr; }
+                if (h->d_stream) { (void)hipFree(h->d_stream); h->d_stream = nullptr; }
+                for (DevBuf *b : {&ctx->bam_comp, &ctx->bam_stream, &ctx->bam_work}) if (b->p) { (void)hipFree(b->p); *b = DevBuf(); }
             }
-            prev_clean = (o.flags & 3) == 0;
         }
-        if (!repaired) {
-            bool any = false;
-            for (auto &o : hso) if (o.flags & 3) any = true;
-            if (!any) break;
-        }
-        if (timing) fprintf(stderr, "[phz timing]     bam device: %d guessed record boundaries were fakes, repaired from the preceding chain (pass %d)\n", repaired, pass);
-        if (pass == 7) return fail(PHZ_E_UNSUPPORTED, "record boundaries did not converge");
-        if (hipStreamSynchronize(sm) != hipSuccess) return fail(PHZ_E_HIP, "boundary repair");
+        if (!got) return fail(PHZ_E_NOMEM, "device BAM buffers");
+        lap("device buffers");
+        return PHZ_OK;
     }
-    hipLaunchKernelGGL(k_seg_kept, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, sm, (const SegOut *)dso, nseg, dkept);
-    if (int s2 = scan_excl(ctx, dkept, dkbase, nseg, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
-    if (hipMemcpyAsync(&total_kept, dkbase + nseg, 4, hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
-        return fail(PHZ_E_HIP, "segment read-back");
-    {   // records sorted (inside segments and across them); 64-bit totals within the 32-bit scans
+    uint32_t *d_crc() const { return (uint32_t *)((char *)d_mem + L.mem.size() * sizeof(phz_bgzf_member)); }
+    // ---- 4. upload of the member table, the CRC32s and the cleared status word on the ctx stream.  (The wall-clock figure of the summary line starts here, and
+    // the copy streams are made here: ncopy of them, one per host thread of copy_chunk)
+    int upload_tables() {
+        t_h2d0 = Clock::now();
+        for (int t = 0; t < knobs.ncopy; t++) if (hipStreamCreateWithFlags(&cs[t], hipStreamNonBlocking) != hipSuccess) cs[t] = nullptr;
+        if (phz_reserve(ctx, ctx->scalars, 64) != PHZ_OK ||
+            phz_reserve(ctx, ctx->scratch[SC_INFLATE_LENS], L.mem.size() * (size_t)phz_inflate_scratch_bytes_per_member()) != PHZ_OK) return fail(PHZ_E_NOMEM, nullptr);
+        d_status = (int *)ctx->scalars.p;
+        (void)hipMemsetAsync(d_status, 0, 4, sm);
+        (void)hipMemcpyAsync(d_mem, L.mem.data(), L.mem.size() * sizeof(phz_bgzf_member), hipMemcpyHostToDevice, sm);
+        // every member's output is checked against the CRC32 of its trailer after it has been inflated (htslib does, so the reference's `samtools view` stops on a
+        // damaged file that is still valid DEFLATE)
+        if (knobs.crc) (void)hipMemcpyAsync(d_crc(), L.crcs.data(), L.crcs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, sm);
+        (void)hipEventRecord(e0, sm);
+        return PHZ_OK;
+    }
+    // ---- 5. copy + inflate pipeline.  H2D and K_inflate overlapped: the members go over chunk by chunk on the copy streams, and each chunk's members are inflated
+    // as soon as its bytes have arrived -- on n_is streams in turn, so that a chunk's members start while the previous launches are still running (BamKnobs) and the
+    // copy of chunk c + 1 runs while chunk c inflates.  Then the verdict on the status word.
+    int copy_and_inflate() {
+        if (int st = reserve_staging()) return st;
+        start_inflate_streams();
+        for (const BamChunk &c : L.chunks) {
+            if (int st = copy_chunk(c)) return st;
+            hipStream_t si = n_is > 1 ? is[(size_t)(n_launch % n_is)] : sm;
+            int st = phz_inflate_launch(ctx, (const uint8_t *)d_comp, (const phz_bgzf_member *)d_mem, (int64_t)c.first, (int64_t)c.count, (uint8_t *)h->d_stream,
+                                        (uint8_t *)ctx->scratch[SC_INFLATE_LENS].p, d_status, si);
+            if (st == PHZ_OK && knobs.crc) st = phz_crc_launch(ctx, (const phz_bgzf_member *)d_mem, (int64_t)c.first, (int64_t)c.count, (const uint8_t *)h->d_stream, d_crc(), d_status, si);
+            n_launch++;
+            if (st != PHZ_OK) return fail(st, nullptr);
+        }
+        return verdict();
+    }
+    // page-locked staging: ncopy threads x 2 buffers, kept in the ctx for the next BAM of the sample, one event per buffer; without it the mapped file
+    int reserve_staging() {
+        fd = ::open(path, O_RDONLY);
+        stage_ok = fd >= 0 && phz_reserve_host(ctx, ctx->h_bam_stage, (size_t)knobs.ncopy * 2 * knobs.stage_bytes) == PHZ_OK;
+        if (!stage_ok) {
+            (void)hipGetLastError();
+            if (!phz_bam_plan_map(&plan)) return fail(PHZ_E_NOMEM, nullptr);          // no page-locked staging and no mapping either
+        }
+        for (int t = 0; t < knobs.ncopy * 2; t++) if (stage_ok && hipEventCreateWithFlags(&stage_ev[t], hipEventDisableTiming) != hipSuccess) stage_ev[t] = nullptr;
+        return PHZ_OK;
+    }
+    void start_inflate_streams() {
+        n_is = knobs.inflate_streams;
+        is.assign((size_t)n_is, nullptr);
+        if (n_is == 1) return;
+        (void)hipStreamSynchronize(sm);                  // the member table and the cleared status word are on the device before any other stream reads them
+        bool all = true;
+        for (auto &s : is) if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { s = nullptr; all = false; }
+        if (!all) { drop_inflate_streams(); n_is = 1; }          // one stream could not be made: every stream that was goes away again, the chunks take the ctx stream
+    }
+    // The chunk goes over in ncopy slices, each read by its own host thread with pread() into page-locked staging buffers of its own (two per thread, in turn: a
+    // buffer is refilled once the event of its last copy has passed) and sent on its own stream.  Copying out of the mapped file instead -- pageable memory, staged
+    // by the runtime at ~13 GB/s per thread -- also populated a page-table entry for every page of the file: 0.16 s of munmap afterwards for a 3.8 GB BAM, on top
+    // of 0.34 s for the copy; it is what remains when the staging memory cannot be reserved.  Returns when the chunk is on the device.
+    int copy_chunk(const BamChunk &c) {
+        char *dst = (char *)d_comp + L.comp_at(c), *stage = (char *)ctx->h_bam_stage.p;
+        const uint64_t a = c.a, len = c.b - c.a, SB = knobs.stage_bytes;
+        const int nsl = (cs[0] && stage_ok && len >= knobs.slice_min) ? knobs.ncopy : 1;
+        std::vector<std::thread> th;
+        std::vector<int> thst((size_t)nsl, PHZ_OK), rounds((size_t)nsl, 0);
+        for (int t = 0; t < nsl; t++)
+            th.emplace_back([&, t] {
+                (void)hipSetDevice(ctx->device);
+                const uint64_t lo = (len * (uint64_t)t / (uint64_t)nsl) & ~(uint64_t)4095, hi = t + 1 == nsl ? len : ((len * (uint64_t)(t + 1) / (uint64_t)nsl) & ~(uint64_t)4095);
+                hipStream_t s2 = cs[t] ? cs[t] : sm;
+                if (!stage_ok) {
+                    if (hipMemcpyAsync(dst + lo, plan.file + a + lo, hi - lo, hipMemcpyHostToDevice, s2) != hipSuccess) thst[(size_t)t] = PHZ_E_HIP;
+                    (void)hipStreamSynchronize(s2);
+                    return;
+                }
+                int which = 0;
+                for (uint64_t o = lo; o < hi; o += SB, which ^= 1) {
+                    const uint64_t m = hi - o < SB ? hi - o : SB;
+                    char *sb = stage + ((size_t)t * 2 + (size_t)which) * SB;
+                    const hipEvent_t ev = stage_ev[(size_t)t * 2 + (size_t)which];
+                    if (ev && hipEventSynchronize(ev) != hipSuccess) { thst[(size_t)t] = PHZ_E_HIP; return; }
+                    uint64_t got = 0;
+                    while (got < m) {
+                        const ssize_t r = pread(fd, sb + got, (size_t)(m - got), (off_t)(a + o + got));
+                        if (r <= 0) { thst[(size_t)t] = PHZ_E_ARG; return; }
+                        got += (uint64_t)r;
+                    }
+                    if (hipMemcpyAsync(dst + o, sb, m, hipMemcpyHostToDevice, s2) != hipSuccess) { thst[(size_t)t] = PHZ_E_HIP; return; }
+                    if (ev) (void)hipEventRecord(ev, s2);
+                    else (void)hipStreamSynchronize(s2);
+                    rounds[(size_t)t]++;
+                }
+                (void)hipStreamSynchronize(s2);                   // the slice is on the device (and the staging buffers are free again)
+            });
+        for (auto &x : th) x.join();
+        n_slices += nsl;
+        for (int r : rounds) n_rounds += r;
+        for (int v : thst) if (v != PHZ_OK) return fail(v, nullptr);
+        return PHZ_OK;
+    }
+    int verdict() {
+        drop_inflate_streams();
+        (void)hipEventRecord(e1, sm);
+        int bad = 0;
+        (void)hipMemcpyAsync(&bad, d_status, 4, hipMemcpyDeviceToHost, sm);
+        (void)hipStreamSynchronize(sm);
+        drop_copy_streams(); drop_staging();
+        h2d_ms = std::chrono::duration<double, std::milli>(Clock::now() - t_h2d0).count();
+        (void)hipEventElapsedTime(&inflate_ms, e0, e1);
+        ctx->last_ms[PHZ_T_INFLATE] = inflate_ms; ctx->total_ms[PHZ_T_INFLATE] += inflate_ms; ctx->launches[PHZ_T_INFLATE]++;
+        drop_compressed();
+        if (bad) return fail(PHZ_E_UNSUPPORTED, bad == 7 ? "a BGZF member does not give the CRC32 of its trailer" : "a BGZF member is not valid DEFLATE");
+        lap("H2D + K_inflate (+ free of the compressed copy)");
+        phz_bam_plan_release(&plan);         // closes the file (nothing was mapped unless the fallback copied out of a mapping)
+        lap("release of the plan");
+        return PHZ_OK;
+    }
+    // ---- 6. segments: the list, the mask of the wanted references and the filters on the device, the guessed first boundary of every segment
+    int segments() {
+        nseg = (int64_t)L.segs.size(); gseg = (unsigned)((nseg + 63) / 64);
+        seg = SegCarve(nseg, n_ref);
+        if (hipMalloc(&d_seg, seg.bytes) != hipSuccess) { d_seg = nullptr; return fail(PHZ_E_NOMEM, "device BAM segments"); }
+        mask.assign((size_t)n_ref, ref_names ? 0 : 1);
+        if (ref_names) for (int i = 0; i < n_ref; i++) for (int k = 0; k < n_names; k++) if (h->refs[(size_t)i].first == ref_names[k]) mask[(size_t)i] = 1;
+        if (hipMemcpyAsync(seg.segs(d_seg), L.segs.data(), (size_t)nseg * sizeof(Seg), hipMemcpyHostToDevice, sm) != hipSuccess ||
+            hipMemcpyAsync(seg.mask(d_seg), mask.data(), (size_t)n_ref, hipMemcpyHostToDevice, sm) != hipSuccess) return fail(PHZ_E_HIP, "hipMemcpyAsync");
+        F.min_mapq = f->min_mapq; F.flag_required = f->flag_required; F.flag_forbidden = f->flag_forbidden; F.isize_cutoff = f->isize_cutoff;
+        F.ref_mask = seg.mask(d_seg); F.n_ref = n_ref;
+        (void)hipEventRecord(e0, sm);
+        hipLaunchKernelGGL(k_seg_start, dim3(gseg), dim3(64), 0, sm, (const uint8_t *)h->d_stream, (const Seg *)seg.segs(d_seg), nseg, n_ref, seg.start(d_seg));
+        return PHZ_OK;
+    }
+    // ---- 7. The counting hop, repeated while a guessed boundary turns out to be a fake (a byte pattern inside a record that passes the plausibility chain):
+    // segment k's chain is the truth when its own start is, so where it ARRIVES becomes the start of segment k + 1, and the hop runs again.  Every boundary is
+    // verified in the end, or the file goes to the host path.  Then the kept counts of the segments, scanned.
+    int counting_hop() {
+        const uint8_t *d = (const uint8_t *)h->d_stream;
+        const Seg *dsegs = seg.segs(d_seg); uint64_t *dstart = seg.start(d_seg); SegOut *dso = seg.so(d_seg);
+        const auto &segs = L.segs;
+        hso.resize((size_t)nseg);
+        for (int pass = 0;; pass++) {
+            hipLaunchKernelGGL(k_hop<0>, dim3(gseg), dim3(64), 0, sm, d, dsegs, nseg, (const uint64_t *)dstart, F, dso, (const uint32_t *)nullptr, KeptOut{});
+            if (hipMemcpyAsync(hso.data(), dso, (size_t)nseg * sizeof(SegOut), hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
+                return fail(PHZ_E_HIP, "segment read-back");
+            int repaired = 0;
+            bool prev_clean = true;
+            for (int64_t k = 0; k < nseg; k++) {
+                const SegOut &o = hso[(size_t)k];
+                const bool last_of_piece = !(k + 1 < nseg && segs[(size_t)k + 1].piece == segs[(size_t)k].piece);
+                if ((o.flags & 1) && prev_clean) return fail(PHZ_E_ARG, "truncated or corrupt BAM record");
+                if ((o.flags & 2) && prev_clean) {
+                    if (last_of_piece) return fail(PHZ_E_ARG, "truncated or corrupt BAM record");      // ran past the end of the piece
+                    if (hipMemcpyAsync(dstart + k + 1, &hso[(size_t)k].end_pos, 8, hipMemcpyHostToDevice, sm) != hipSuccess) return fail(PHZ_E_HIP, "boundary repair");
+                    repaired++;
+                }
+                prev_clean = (o.flags & 3) == 0;
+            }
+            if (!repaired) {
+                bool any = false;
+                for (auto &o : hso) if (o.flags & 3) any = true;
+                if (!any) break;
+            }
+            if (knobs.timing) fprintf(stderr, "[phz timing]     bam device: %d guessed record boundaries were fakes, repaired from the preceding chain (pass %d)\n", repaired, pass);
+            if (pass == 7) return fail(PHZ_E_UNSUPPORTED, "record boundaries did not converge");
+            if (hipStreamSynchronize(sm) != hipSuccess) return fail(PHZ_E_HIP, "boundary repair");
+        }
+        hipLaunchKernelGGL(k_seg_kept, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, sm, (const SegOut *)dso, nseg, seg.kept(d_seg));
+        if (int s2 = scan_excl(ctx, seg.kept(d_seg), seg.kbase(d_seg), nseg, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+        if (hipMemcpyAsync(&total_kept, seg.kbase(d_seg) + nseg, 4, hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
+            return fail(PHZ_E_HIP, "segment read-back");
+        return PHZ_OK;
+    }
+    // ---- 8. host checks: records sorted (inside segments and across them); 64-bit totals within the 32-bit scans
+    int host_checks() {
         int32_t lr = -2, lp = 0;
         uint64_t sum = 0, sq = 0, qn = 0, ops = 0;
-        for (int64_t k = 0; k < nseg; k++) {
-            const SegOut &o = hso[(size_t)k];
+        for (const SegOut &o : hso) {
             if (o.flags & 4) return fail(PHZ_E_UNSUPPORTED, "BAM is not coordinate-sorted");
             if (o.first_ref != -2) {
                 if (lr != -2 && (o.first_ref < lr || (o.first_ref == lr && o.first_pos < lp))) return fail(PHZ_E_UNSUPPORTED, "BAM is not coordinate-sorted");
@@ -800,56 +870,67 @@ int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names
             }
             sum += o.kept; sq += o.sq_sum; qn += o.qn_sum; ops += o.op_sum;
         }
-        uint64_t lim = (1ull << 32) - 16;
-        { const char *e = getenv("PHZ_BAMDEV_LIMIT"); if (e) lim = (uint64_t)atoll(e); }      // tests lower it to exercise the caller's split
-        if (sum >= (1ull << 31) || sq >= lim || qn >= lim || ops >= lim)
+        if (sum >= (1ull << 31) || sq >= knobs.limit || qn >= knobs.limit || ops >= knobs.limit)
             return fail(PHZ_E_UNSUPPORTED, "call exceeds the 32-bit offsets of the device path");
+        lap("segments + counting hop");
+        return PHZ_OK;
     }
-    lap("segments + counting hop");
-    const int64_t nk = (int64_t)total_kept;
-    h->n_kept = nk;
-    // ---- kept-record list + prefix sums
-    const size_t NK = (size_t)(nk ? nk : 1);
-    const size_t a8 = (NK * 8 + 255) & ~(size_t)255, a4 = ((NK + 1) * 4 + 255) & ~(size_t)255, rb = ((size_t)(n_ref + 2) * 8 + 255) & ~(size_t)255;
-    h->d_work = bam_take(&ctx->bam_work, a8 + 8 * a4 + rb, &h->d_work_cap);          // (kept between BAMs like the two stream buffers: this ~1 GB hipMalloc took 0.38 s now and then)
-    if (!h->d_work) return fail(PHZ_E_NOMEM, "device BAM record list");
-    char *w = (char *)h->d_work;
-    h->K.off = (uint64_t *)w; w += a8;
-    h->K.ref = (int32_t *)w; w += a4;
-    h->K.nops = (uint32_t *)w; w += a4; h->K.sq = (uint32_t *)w; w += a4; h->K.nb = (uint32_t *)w; w += a4; h->K.lqn = (uint32_t *)w; w += a4;
-    h->co = (uint32_t *)w; w += a4; h->so = (uint32_t *)w; w += a4; h->qo = (uint32_t *)w; w += a4;
-    h->d_ref_begin = (int64_t *)w;
-    if (nk > 0) {
-        hipLaunchKernelGGL(k_hop<1>, dim3(gseg), dim3(64), 0, sm, d, (const Seg *)dsegs, nseg, (const uint64_t *)dstart, F, dso, (const uint32_t *)dkbase, h->K);
-        if (int s2 = scan_excl(ctx, h->K.nops, h->co, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
-        if (int s2 = scan_excl(ctx, h->K.sq, h->so, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
-        if (int s2 = scan_excl(ctx, h->K.lqn, h->qo, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
-    } else {
-        (void)hipMemsetAsync(h->co, 0, 4, sm); (void)hipMemsetAsync(h->so, 0, 4, sm); (void)hipMemsetAsync(h->qo, 0, 4, sm);
+    // ---- 9. kept-record list (the writing hop), the three prefix sums over it, the first record of every reference
+    int kept_list() {
+        const int64_t nk = h->n_kept = (int64_t)total_kept;
+        const KeptCarve work(nk, n_ref);
+        h->d_work = bam_take(&ctx->bam_work, work.bytes(), &h->d_work_cap, knobs.keep_buffers);          // (kept between BAMs like the two stream buffers: this ~1 GB hipMalloc took 0.38 s now and then)
+        if (!h->d_work) return fail(PHZ_E_NOMEM, "device BAM record list");
+        work.point(h);
+        if (nk > 0) {
+            hipLaunchKernelGGL(k_hop<1>, dim3(gseg), dim3(64), 0, sm, (const uint8_t *)h->d_stream, (const Seg *)seg.segs(d_seg), nseg, (const uint64_t *)seg.start(d_seg), F,
+                               seg.so(d_seg), (const uint32_t *)seg.kbase(d_seg), h->K);
+            if (int s2 = scan_excl(ctx, h->K.nops, h->co, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+            if (int s2 = scan_excl(ctx, h->K.sq, h->so, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+            if (int s2 = scan_excl(ctx, h->K.lqn, h->qo, nk, ctx->scratch[SC_BAM_SCAN_TMP])) return fail(s2, nullptr);
+        } else {
+            (void)hipMemsetAsync(h->co, 0, 4, sm); (void)hipMemsetAsync(h->so, 0, 4, sm); (void)hipMemsetAsync(h->qo, 0, 4, sm);
+        }
+        hipLaunchKernelGGL(k_ref_bounds, dim3((unsigned)((n_ref + 1 + 63) / 64)), dim3(64), 0, sm, (const int32_t *)h->K.ref, nk, n_ref, h->d_ref_begin);
+        (void)hipEventRecord(e1, sm);
+        return PHZ_OK;
     }
-    hipLaunchKernelGGL(k_ref_bounds, dim3((unsigned)((n_ref + 1 + 63) / 64)), dim3(64), 0, sm, (const int32_t *)h->K.ref, nk, n_ref, h->d_ref_begin);
-    (void)hipEventRecord(e1, sm);
-    if (hipMemcpyAsync(h->ref_begin.data(), h->d_ref_begin, (size_t)(n_ref + 1) * 8, hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
-        return fail(PHZ_E_HIP, "reference bounds read-back");
-    // totals must fit the 32-bit offsets of the scans: 64-bit sums of the per-segment kept counts are fine, the byte sums are
-    // checked through the per-reference values (a wrapped scan makes a reference's span negative or absurd)
-    for (int r = 0; r <= n_ref; r++) {
-        const int64_t i = h->ref_begin[(size_t)r];
-        (void)hipMemcpyAsync(&h->h_co[(size_t)r], h->co + i, 4, hipMemcpyDeviceToHost, sm);
-        (void)hipMemcpyAsync(&h->h_so[(size_t)r], h->so + i, 4, hipMemcpyDeviceToHost, sm);
-        (void)hipMemcpyAsync(&h->h_qo[(size_t)r], h->qo + i, 4, hipMemcpyDeviceToHost, sm);
+    // ---- 10. read-backs (reference bounds, then the three offsets at every bound: what phz_bamdev_sizes_of answers from) and the timing
+    int read_backs() {
+        if (hipMemcpyAsync(h->ref_begin.data(), h->d_ref_begin, (size_t)(n_ref + 1) * 8, hipMemcpyDeviceToHost, sm) != hipSuccess || hipStreamSynchronize(sm) != hipSuccess)
+            return fail(PHZ_E_HIP, "reference bounds read-back");
+        // totals must fit the 32-bit offsets of the scans: 64-bit sums of the per-segment kept counts are fine, the byte sums are
+        // checked through the per-reference values (a wrapped scan makes a reference's span negative or absurd)
+        for (int r = 0; r <= n_ref; r++) {
+            const int64_t i = h->ref_begin[(size_t)r];
+            (void)hipMemcpyAsync(&h->h_co[(size_t)r], h->co + i, 4, hipMemcpyDeviceToHost, sm);
+            (void)hipMemcpyAsync(&h->h_so[(size_t)r], h->so + i, 4, hipMemcpyDeviceToHost, sm);
+            (void)hipMemcpyAsync(&h->h_qo[(size_t)r], h->qo + i, 4, hipMemcpyDeviceToHost, sm);
+        }
+        if (hipStreamSynchronize(sm) != hipSuccess) return fail(PHZ_E_HIP, "offset read-back");
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        ctx->last_ms[PHZ_T_BAMPACK] = ms; ctx->total_ms[PHZ_T_BAMPACK] += ms; ctx->launches[PHZ_T_BAMPACK]++;
+        drop_segments();
+        lap("kept-record list + scans");
+        if (knobs.timing)
+            fprintf(stderr, "[phz timing]     bam device: H2D of %.1f MB overlapped with K_inflate (%.1f MB out): %.1f ms wall, first launch to last %.1f ms; boundaries + hop + scans %.1f ms, %lld records kept; "
+                            "%d chunks, %d copy slices, %lld staging rounds\n",
+                    L.comp_bytes / 1e6, L.out_bytes / 1e6, h2d_ms, inflate_ms, ms, (long long)h->n_kept, n_launch, n_slices, n_rounds);
+        return PHZ_OK;
     }
-    if (hipStreamSynchronize(sm) != hipSuccess) return fail(PHZ_E_HIP, "offset read-back");
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    ctx->last_ms[PHZ_T_BAMPACK] = ms; ctx->total_ms[PHZ_T_BAMPACK] += ms; ctx->launches[PHZ_T_BAMPACK]++;
-    (void)hipFree(d_seg);
-    lap("kept-record list + scans");
-    if (timing)
-        fprintf(stderr, "[phz timing]     bam device: H2D of %.1f MB overlapped with K_inflate (%.1f MB out): %.1f ms wall, first launch to last %.1f ms; boundaries + hop + scans %.1f ms, %lld records kept\n",
-                comp_bytes / 1e6, out_bytes / 1e6, h2d_ms, inflate_ms, ms, (long long)nk);
-    *out = h;
-    return PHZ_OK;
+};
+
+}  // namespace
+
+extern "C" {
+
+int phz_bamdev_open(phz_ctx *ctx, const char *path, const char *const *ref_names, int n_names, const phz_bam_filters *f, phz_bamdev **out) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || !path || !f || !out) return PHZ_E_ARG;
+    *out = nullptr;
+    BamOpen call(ctx, path, ref_names, n_names, f, out);
+    return call.run();
 }
 
 int phz_bamdev_close(phz_bamdev *h) { delete h; return PHZ_OK; }

@@ -376,3 +376,107 @@ def test_deep_bam_is_decoded_in_chromosome_halves(ctx, tmp_path, monkeypatch):
     _same(host, {c: dev[c] for c in host}, "split")
     monkeypatch.setenv("PHZ_BAMDEV_LIMIT", "1000")                # nothing fits: declined, the host path takes over
     assert bamio.shards_from_bam_device(ctx, path, {}, 0, False, False) is None
+
+
+# ---- the pipeline as the real workload runs it (several K_inflate launches on several streams, every chunk copied in slices through the page-locked staging
+# buffers), reached by a 4 MB file: 1 MiB chunks, 64 KB slices and 64 KB staging buffers instead of 1,280 MB / 64 MB / 8 MB
+CHUNKED = {"PHZ_BAM_CHUNK_MB": "1", "PHZ_BAM_INFLATE_STREAMS": "3", "PHZ_BAM_NCOPY": "3", "PHZ_BAM_SLICE_MIN_KB": "64", "PHZ_BAM_STAGE_KB": "64", "PHZ_TIMING": "1"}
+SUMMARY = r"bam device: H2D of [0-9.]+ MB overlapped with K_inflate .* (\d+) records kept; (\d+) chunks, (\d+) copy slices, (\d+) staging rounds\n"
+
+
+def _summary_lines(capfd):
+    """(records kept, chunks launched, copy slices, staging rounds) of every phz_bamdev_open since the last look"""
+    import re
+    return [tuple(int(x) for x in m) for m in re.findall(SUMMARY, capfd.readouterr().err)]
+
+
+@pytest.fixture(scope="module")
+def big_bam(tmp_path_factory):
+    """A two-chromosome BAM of at least 3 MiB and the host decoder's shards of it, whole and restricted to chr22 (with the interners of each)."""
+    from phaser_amd import bamio
+    path = _two_chrom_bam(tmp_path_factory.mktemp("big"), 20000, 30000)
+    hi = {}; hi22 = {}
+    host = bamio.shards_from_bam_native(path, hi, 0, False, False, 0.0, threads=2)
+    host22 = bamio.shards_from_bam_native(path, hi22, 0, False, False, 0.0, chroms={"chr22"}, threads=2)
+    return path, {None: (host, hi), "chr22": (host22, hi22)}
+
+
+def test_chunked_multi_stream_staged_pipeline_equals_host_decoder(ctx, big_bam, monkeypatch, capfd):
+    """1 MiB chunks on three inflate streams, every chunk in three slices through 64 KB staging buffers: the shards are the host decoder's array by array, whole
+    file and chromosome-restricted.  The summary line's counters show that the path was taken: >= 3 launches, three slices per chunk, and more than two
+    staging rounds per slice on average -- a thread has two buffers, so every thread refilled a buffer and waited on its event first (a 1 MiB chunk in three
+    slices of ~340 KB takes ~6 rounds of 64 KB per slice)."""
+    from phaser_amd import bamio
+    path, want = big_bam
+    assert os.path.getsize(path) >= 3 << 20
+    for k, v in CHUNKED.items():
+        monkeypatch.setenv(k, v)
+    _summary_lines(capfd)
+    for chroms in (None, {"chr22"}):
+        host, hi = want[None if chroms is None else "chr22"]
+        di = {}
+        dev = bamio.shards_from_bam_device(ctx, path, di, 0, False, False, 0.0, chroms=chroms)
+        assert dev is not None
+        _same(host, dev, chroms)
+        assert sorted(hi) == sorted(di)
+        for c in hi:
+            assert hi[c].names == di[c].names
+        (kept, chunks, slices, rounds), = _summary_lines(capfd)
+        print("chroms", chroms, "kept", kept, "chunks", chunks, "slices", slices, "staging rounds", rounds)
+        assert kept == sum(s.n for s in host.values())
+        assert rounds > 2 * slices
+        if chroms is None:
+            assert chunks >= 3 and slices == 3 * chunks
+
+
+def test_cleanup_with_streams_in_flight(ctx, big_bam, tmp_path, monkeypatch):
+    """A damaged member (one bit of its trailer's CRC32, as in test_device_path_refuses_damaged_bgzf_members) in the third of four chunks: chunks before it have been
+    launched on other inflate streams when the status word is read.  The device path declines (an error code for bad input, nothing else), every stream, event and
+    buffer of the call is released, and the same ctx then decodes the good file and launches K_map."""
+    import torch
+    from phaser_amd import bamio
+    from phaser_amd.mapper import Mapper
+    path, want = big_bam
+    host, _ = want[None]
+    raw = bytearray(open(path, "rb").read())
+    assert len(raw) >= 3 << 20
+    off = 0; members = []
+    while off + 18 <= len(raw):
+        bsize = int.from_bytes(raw[off + 16:off + 18], "little") + 1
+        members.append((off, bsize)); off += bsize
+    off, bsize = members[len(members) * 5 // 8]              # ~2.5 MB into the file: the third 1 MiB chunk
+    assert off > 2 << 20
+    raw[off + bsize - 8] ^= 0x10
+    bad = str(tmp_path / "bad.bam")
+    open(bad, "wb").write(bytes(raw))
+    for k, v in CHUNKED.items():
+        monkeypatch.setenv(k, v)
+    assert bamio.shards_from_bam_device(ctx, bad, {}, 0, False, False, 0.0) is None
+    dev = bamio.shards_from_bam_device(ctx, path, {}, 0, False, False, 0.0)           # the same ctx right after the failure
+    assert dev is not None
+    _same(host, dev, "after a refused file")
+    c = next(iter(dev))
+    vpos = torch.arange(1000, 2_000_000, 5000, dtype=torch.int32)
+    calls = Mapper(0, ctx=ctx).map(dev[c], vpos, 10)                                  # a kernel launch + its error check on this ctx
+    assert calls.n >= 0
+
+
+def test_register_switch_is_gone(ctx, tmp_path, monkeypatch, capfd):
+    """PHZ_BAM_REGISTER (the mapped file registered with the runtime: measured, lost, deleted) is ignored: same shards, same stage lines."""
+    import re
+    from phaser_amd import bamio
+    path = _two_chrom_bam(tmp_path)
+    host = bamio.shards_from_bam_native(path, {}, 0, False, False, threads=2)
+    monkeypatch.setenv("PHZ_TIMING", "1")
+    forms = []
+    for reg in (None, "1"):
+        if reg:
+            monkeypatch.setenv("PHZ_BAM_REGISTER", reg)
+        capfd.readouterr()
+        dev = bamio.shards_from_bam_device(ctx, path, {}, 0, False, False)
+        assert dev is not None
+        _same(host, dev, ("PHZ_BAM_REGISTER", reg))
+        lines = [l for l in capfd.readouterr().err.split("\n") if "bam device:" in l]
+        assert len(re.findall(SUMMARY, "\n".join(lines) + "\n")) == 1 and not any("registration" in l for l in lines)
+        forms.append([re.sub(r"[0-9.]+", "#", l) for l in lines])
+    assert forms[0] == forms[1]
