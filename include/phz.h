@@ -850,9 +850,9 @@ int phz_microbench(phz_ctx *ctx, int kind, int waves_per_simd, int iters, double
 int phz_selftest_sort(phz_ctx *ctx, int key_bytes, const void *keys, const uint32_t *vals, int64_t n, const int32_t *ranges, int nranges, int three_launch,
                       void *keys_out, uint32_t *vals_out);
 
-/* Self-test of the library's device exclusive scans (out[i] = sum of in[0 .. i), out[n] = total): impl 0 = the three-launch scan of 32-bit counts
- * (phz_scan.h), 1 = the generic scan as its own dispatch chooses (one launch with decoupled look-back for 32-bit sums below 4 Mi elements, three launches
- * otherwise), 2 = the generic scan forced onto the three launches.  Host arrays in and out: n values of in_bytes (4 or 8), sums of out_bytes (4, 8, or 8
+/* Self-test of the library's device exclusive scan, gscan_excl of phz_scan.h (out[i] = sum of in[0 .. i), out[n] = total): impl 1 = the scan as its own
+ * dispatch chooses (one launch with decoupled look-back for 32-bit sums below 4 Mi elements, three launches otherwise), 2 = the scan forced onto the three
+ * launches.  impl 0 was an older three-launch scan of 32-bit counts that phz_scan.h no longer holds: PHZ_E_ARG.  Host arrays in and out: n values of in_bytes (4 or 8), sums of out_bytes (4, 8, or 8
  * from 4-byte values); transform 1 scans the decimal label width of the values (digits + 1; 32-bit only) in place of the values themselves.  in_skew /
  * out_skew (0..3): elements between a 16-byte aligned device address and the arrays, in_place: the sums replace the input (one width, one skew).
  * epoch_preset >= 0 sets the ctx's scan epoch before the call (a fresh ctx only, to a value above every epoch it has used), -1 leaves it.  out holds

@@ -4,7 +4,7 @@
 // A gene with n GW entries and m PG entries has n^2 + m^2 ordered pairs: pair p < n^2 belongs to the first pass (a = p / n, b = p % n), the others
 // to the second (q = p - n^2, a = n + q / m, b = n + q % m).  The host driver cuts every pass into TILES of PHZ_ANNOT_TILE consecutive pairs (a tile never
 // holds pairs of two genes or of two passes); a workgroup owns a tile, a thread a pair.  k_annot<false> reduces the rows of a tile's pairs (0..8 each) to one
-// total per tile, scan_excl turns the totals of a batch's tiles into bases, k_annot<true> recomputes the pairs, takes a workgroup exclusive scan
+// total per tile, gscan_excl (phz_scan.h) turns the totals of a batch's tiles into bases, k_annot<true> recomputes the pairs, takes a workgroup exclusive scan
 // and writes every pair's records at base + local offset: no per-pair value reaches memory and no atomic decides a position, so the records come out in the
 // reference's order whatever the schedule.
 //
@@ -149,7 +149,7 @@ template <bool FILL> __global__ __launch_bounds__(THREADS) void k_annot(AnnotArg
         __syncthreads();
         if (tid == 0) a.tile_count[tile] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
     } else {
-        const uint32_t incl = wave_incl_scan(c, lane);
+        const uint32_t incl = gs_wave_incl(c, lane);
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
         uint32_t at = a.tile_base[a.b0 + blockIdx.x] + incl - c;
@@ -264,7 +264,8 @@ extern "C" int phz_annot_pairs(phz_ctx *ctx, const phz_annot_in *in, int64_t bat
             if (int s = phz_reserve(ctx, ctx->scratch[SC_ANNOT_OUT], (size_t)r * sizeof(uint4))) return s;
             a.t0 = t0; a.tile_base = (const uint32_t *)ctx->scratch[SC_ANNOT_BASE].p; a.out = (uint4 *)ctx->scratch[SC_ANNOT_OUT].p;
             (void)hipEventRecord(ctx->ev0, sm);
-            if (int s = scan_excl(ctx, a.tile_count + t0, (uint32_t *)ctx->scratch[SC_ANNOT_BASE].p, nt, ctx->scratch[SC_ANNOT_SCAN_TMP])) return s;
+            // (a batch starts at any tile: the scan's input pointer is 16-byte aligned or not as t0 falls, gscan_excl takes either)
+            if (int s = gscan_excl<uint32_t, uint32_t>(ctx, a.tile_count + t0, (uint32_t *)ctx->scratch[SC_ANNOT_BASE].p, nt, ctx->scratch[SC_ANNOT_SCAN_TMP])) return s;
             for (a.b0 = 0; a.b0 < nt; a.b0 += PHZ_ANNOT_GRID) {
                 hipLaunchKernelGGL(k_annot<true>, dim3((unsigned)std::min<int64_t>(PHZ_ANNOT_GRID, nt - a.b0)), dim3(THREADS), 0, sm, a);
                 PHZ_HIP(ctx, hipGetLastError());

@@ -575,7 +575,8 @@ struct GenCall {
         a.wl = scr<uint32_t>(SC_GEN_WORKLIST); a.wl_n = scr<uint32_t>(SC_GEN_WORKLIST_N);
         return PHZ_OK;
     }
-    // ---- windows, variant descriptors, the count pass and its list pass, the two scans of the tile sums
+    // ---- windows, variant descriptors, the count pass and its list pass, the two scans of the tile sums (cb and tb are 16-byte aligned or not as grid falls:
+    // gscan_excl takes either)
     int count_and_scan() {
         PHZ_HIP(ctx, hipMemsetAsync(a.wl_n, 0, 4, sm));
         PHZ_HIP(ctx, hipEventRecord(ctx->ev0, sm));
@@ -583,8 +584,8 @@ struct GenCall {
         hipLaunchKernelGGL(k_gen_desc, dim3(nblk(nv)), dim3(256), 0, sm, a.ref_len, a.aoff, a.abytes, (int)nv, scr<uint32_t>(SC_GEN_DESC));
         hipLaunchKernelGGL(k_map_general, dim3(grid), dim3(256), 0, sm, a);
         hipLaunchKernelGGL(k_map_general_list<false>, dim3(2048), dim3(256), 0, sm, a);     // grid-stride over a list whose length only the device knows
-        if (int s = scan_excl(ctx, a.tile_calls, cb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
-        return scan_excl(ctx, a.tile_text, tb, (int64_t)grid, S[SC_GEN_SCAN_TMP]);
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, a.tile_calls, cb, (int64_t)grid, S[SC_GEN_SCAN_TMP])) return s;
+        return gscan_excl<uint32_t, uint32_t>(ctx, a.tile_text, tb, (int64_t)grid, S[SC_GEN_SCAN_TMP]);
     }
     // ---- WAIT: the list length and the two totals as one PhzMail block; the caller's counts, the PHZ_GEN_DBG line, the time of a call whose emit pass is already
     // behind it (`emitted`), and PHZ_E_CAPACITY when an output is too small for the totals

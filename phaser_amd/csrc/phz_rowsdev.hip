@@ -22,7 +22,6 @@
 
 #include <type_traits>
 #include "phz_internal.h"
-#include "phz_scan.h"
 #include "phz_sort.h"
 #include "phz_text.h"
 #include "phz_uf.h"
@@ -524,11 +523,6 @@ __global__ __launch_bounds__(256) void k_cfg_prefix(RD D, int64_t nblocks, uint3
     }
     blk_bytes[b] = run;
 }
-__device__ __forceinline__ unsigned long long wave_incl_u64(unsigned long long x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long y = __shfl_up(x, d); if (lane >= d) x += y; }
-    return x;
-}
 // the same for the blocks of more than ROW_WAVE_MIN members, one wave per block (the list k_big_blocks made): lanes take members 64 at a time, prefixes by wave scans
 __global__ __launch_bounds__(64) void k_cfg_prefix_wave(RD D, const uint32_t *big_blk, uint32_t *pl, uint32_t *pb, unsigned long long *ps, unsigned long long *blk_bytes) {
     const int64_t b = big_blk[blockIdx.x];
@@ -539,7 +533,7 @@ __global__ __launch_bounds__(64) void k_cfg_prefix_wave(RD D, const uint32_t *bi
         const uint32_t t = t0 + (uint32_t)lane;
         unsigned long long L = 0, B = 0;
         if (t < n) { const MemRec r = D.mrec[m0 + t]; L = cfg_member_len(D, r, m0 + t); B = r.ref_b != 0 ? 1ull : 0ull; }
-        const unsigned long long iL = wave_incl_u64(L, lane), iB = wave_incl_u64(B, lane);
+        const unsigned long long iL = gs_wave_incl(L, lane), iB = gs_wave_incl(B, lane);
         if (t < n) { pl[m0 + t] = (uint32_t)(TL + iL - L); pb[m0 + t] = (uint32_t)(NB + iB - B); }
         TL += __shfl(iL, 63); NB += __shfl(iB, 63);
     }
@@ -553,7 +547,7 @@ __global__ __launch_bounds__(64) void k_cfg_prefix_wave(RD D, const uint32_t *bi
             const bool A = r.ref_a != 0, B = r.ref_b != 0;
             S = (unsigned long long)(n - 1) * (L + 8ull) + (TL - L) + 2ull * ((A ? NB : (unsigned long long)n - NB) - (B == A ? 1ull : 0ull));
         }
-        const unsigned long long iS = wave_incl_u64(S, lane);
+        const unsigned long long iS = gs_wave_incl(S, lane);
         if (t < n) ps[m0 + t] = run + iS - S;
         run += __shfl(iS, 63);
     }
@@ -1083,9 +1077,7 @@ __device__ void phase_general_one(const PH &P, const uint32_t c) {
             int v[4], sum = 0;
 #pragma unroll
             for (int k = 0; k < 4; k++) { const int q = 4 * lane + k; v[k] = q <= n ? s_weak[q] : 0; sum += v[k]; }
-            int incl = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(incl, d); if (lane >= d) incl += y; }
+            const int incl = gs_wave_incl(sum, lane);
             int run = incl - sum;
 #pragma unroll
             for (int k = 0; k < 4; k++) { const int q = 4 * lane + k; run += v[k]; if (q <= n) s_weak[q] = run; }
@@ -1711,9 +1703,7 @@ template <int MODE, int SLOTS, int THREADS, bool HUGE> __device__ void seg_big_o
         const uint32_t chunk = (np + 63u) / 64u, beg = (uint32_t)lane * chunk;
         uint32_t sum = 0;
         for (uint32_t t = beg; t < beg + chunk && t < np; t++) sum += s_pref[t];
-        uint32_t incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d); if (lane >= d) incl += y; }
+        const uint32_t incl = gs_wave_incl(sum, lane);
         uint32_t run = incl - sum;
         for (uint32_t t = beg; t < beg + chunk && t < np; t++) { const uint32_t x = s_pref[t]; s_pref[t] = run; run += x; }
         if (lane == 63) s_pref[np] = incl;
@@ -2787,8 +2777,8 @@ extern "C" int phz_selftest_sort(phz_ctx *ctx, int key_bytes, const void *keys, 
     return fin(e == hipSuccess ? PHZ_OK : phz_fail(ctx, PHZ_E_HIP, "phz_selftest_sort", e));
 }
 
-// Self-test entry of the device exclusive scans: scan_excl of phz_scan.h (impl 0), gscan_excl of phz_sort.h as its own dispatch chooses between the one-launch
-// look-back and the three-launch passes (impl 1), gscan_excl on the three-launch passes whatever the size (impl 2).  The n host values of in_bytes each are
+// Self-test entry of the device exclusive scan, gscan_excl of phz_scan.h: as its own dispatch chooses between the one-launch look-back and the three-launch
+// passes (impl 1), on the three-launch passes whatever the size (impl 2); impl 0 was the older three-launch u32 scan, which left phz_scan.h and is out of this entry's reach (PHZ_E_ARG).  The n host values of in_bytes each are
 // staged in_skew elements behind an aligned device address, the result is written out_skew elements behind one (in_place: into the input buffer, one skew for
 // both), so that the 16-byte accesses of gs_load_rows / gs_store_rows are seen with their alignment gate closed as well as open.  out receives n + 2 values of
 // out_bytes: the n + 1 sums and the element BEHIND the total, which the entry fills with 0xA5 bytes before the scan and no scan may touch.  epoch_preset >= 0:
@@ -2801,7 +2791,7 @@ extern "C" int phz_selftest_scan(phz_ctx *ctx, int impl, int in_bytes, int out_b
         (n && !in) || !out || in_skew < 0 || in_skew > 3 || out_skew < 0 || out_skew > 3 || (transform != 0 && transform != 1) || epoch_preset < -1 ||
         epoch_preset >= (1ll << 30))
         return PHZ_E_ARG;
-    if (impl == 0 && (in_bytes != 4 || out_bytes != 4 || transform)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: scan_excl is a scan of 32-bit values without a transform");
+    if (impl == 0) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: impl 0 (the older three-launch scan of phz_scan.h) no longer exists; 1 and 2 are gscan_excl");
     if (transform && (in_bytes != 4 || out_bytes != 4)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: the LabelWidth transform is instantiated for 32-bit values only");
     if (in_place && (in_bytes != out_bytes || in_skew != out_skew)) return phz_fail(ctx, PHZ_E_ARG, "phz_selftest_scan: in place needs one element width and one skew");
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
@@ -2827,8 +2817,7 @@ extern "C" int phz_selftest_scan(phz_ctx *ctx, int impl, int in_bytes, int out_b
     }
     typedef unsigned long long u64;
     const bool force = impl == 2;
-    if (impl == 0) st = scan_excl(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2]);
-    else if (transform) st = gscan_excl<uint32_t, uint32_t, LabelWidth>(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2], force);
+    if (transform) st = gscan_excl<uint32_t, uint32_t, LabelWidth>(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2], force);
     else if (out_bytes == 4) st = gscan_excl<uint32_t, uint32_t>(ctx, (const uint32_t *)d_in, (uint32_t *)d_out, n, d[2], force);
     else if (in_bytes == 4) st = gscan_excl<uint32_t, u64>(ctx, (const uint32_t *)d_in, (u64 *)d_out, n, d[2], force);
     else st = gscan_excl<u64, u64>(ctx, (const u64 *)d_in, (u64 *)d_out, n, d[2], force);

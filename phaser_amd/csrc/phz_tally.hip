@@ -512,9 +512,7 @@ __global__ __launch_bounds__(TILE_TB) void k_tile(LinesTab T, TileOut O) {
         uint32_t c[TSP], sum = 0;
 #pragma unroll
         for (int j = 0; j < TSP; j++) { c[j] = s_c[tid * TSP + j]; sum += c[j] + (c[j] ? 0x10000u : 0u); }
-        uint32_t incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d); if ((tid & 63) >= d) incl += y; }
+        const uint32_t incl = gs_wave_incl(sum, tid & 63);
         if ((tid & 63) == 63) s_part[tid >> 6] = incl;
         __syncthreads();
         uint32_t base = incl - sum;
@@ -1280,9 +1278,7 @@ __global__ __launch_bounds__(1024) void k_as_percentile(const unsigned long long
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long mine = 0;
     for (int b = 0; b < 64; b++) mine += hist[tid * 64 + b];
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long y = __shfl_up(incl, d); if (lane >= d) incl += y; }
+    unsigned long long incl = gs_wave_incl(mine, lane);
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     unsigned long long before = 0;

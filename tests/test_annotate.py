@@ -616,6 +616,39 @@ def test_kannot_gpu_batches_equal_one_launch(gpu):
     assert e.value.status == _lib.PHZ_E_CAPACITY
 
 
+_BIG = {}
+
+
+def big_case():
+    """500 genes: more than 4,096 tiles of 256 pairs, so the scan of a whole batch's tile counts runs over more than one chunk.  Computed once, never changed"""
+    if not _BIG:
+        T = random_tables(13, n_genes=500)
+        _BIG.update(T=T, ai=tables_to_input(T), want=R.record_tuples(R.all_rows(T)))
+    return _BIG["T"], _BIG["ai"], _BIG["want"]
+
+
+@pytest.mark.gpu
+def test_kannot_gpu_one_batch_of_more_than_one_scan_chunk(gpu):
+    T, ai, want = big_case()
+    stats = {}
+    got = gpu(ai, stats=stats)
+    assert stats["pairs"] == R.pair_count(T) and stats["pairs"] > 4096 * 256 and stats["batches"] == 1
+    assert record_tuples(ai, got) == want
+
+
+@pytest.mark.gpu
+def test_kannot_gpu_batches_that_start_at_any_tile(gpu):
+    """every batch but the first hands the scan `tile_count + t0`: a base pointer that is 16-byte aligned or not as t0 falls"""
+    T, ai, want = big_case()
+    import collections
+    largest = max(collections.Counter(t[0] for t in want).values())          # rows of the largest gene: the smallest capacity the entry accepts
+    for cap in (largest, len(want) // 3 + largest):
+        stats = {}
+        got = gpu(ai, batch_rows=cap, stats=stats)
+        assert stats["batches"] >= 3
+        assert record_tuples(ai, got) == want
+
+
 @pytest.mark.gpu
 def test_kannot_gpu_second_smaller_call_on_one_context(gpu):
     T, ai, want = random_case()

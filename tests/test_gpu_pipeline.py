@@ -959,6 +959,7 @@ def _map_indel_reads(mapper):
     calls, _ = mapper.map_general(soa.pack_readbatch(rb).to("cuda"), torch.from_numpy(vt.pos.astype(np.int32)), torch.from_numpy(vt.ref_len), torch.from_numpy(off),
                                   torch.from_numpy(ab), 10)
     assert calls.n > 5000
+    return calls
 
 
 @pytest.mark.parametrize("between", ["intern_device", "map_reads_general"])

@@ -1,11 +1,11 @@
-"""The device exclusive scans on their own, against numpy.cumsum in uint64 with a leading 0, compared exactly over all n + 1 outputs:
-scan_excl of phaser_amd/csrc/phz_scan.h (impl 0: three launches, u32) and gscan_excl of phz_sort.h as its dispatch chooses (impl 1: the one-launch decoupled
-look-back for 32-bit sums of fewer than 4 Mi elements, three launches otherwise) and forced onto the three launches (impl 2), through phz_selftest_scan.
-Every call also returns the element behind out[n], which the entry fills with 0xA5 bytes and no scan may touch.
+"""The device exclusive scan on its own, against numpy.cumsum in uint64 with a leading 0, compared exactly over all n + 1 outputs: gscan_excl of
+phaser_amd/csrc/phz_scan.h as its dispatch chooses (impl 1: the one-launch decoupled look-back for 32-bit sums of fewer than 4 Mi elements, three launches
+otherwise) and forced onto the three launches (impl 2), through phz_selftest_scan.  impl 0 was an older three-launch u32 scan that phz_scan.h no longer holds (what is left of it is private to
+phz_bamdev.hip and tested through the BAM entry points); the entry refuses the number.  Every call also returns the element behind out[n], which the entry fills with 0xA5 bytes and no scan may touch.
 
 Emulated part (CPU suite): every size class of the chunk / tile / row arithmetic, every instantiated type pair, the LabelWidth transform, skewed base
 pointers, in-place use, one context through scans of very different sizes, the epoch reset, and more than 1,024 chunks (the second trip of the loops of
-k_scan_partials / k_gs_partials, about 8 s per case here, so it stayed in the CPU suite).  The emulation runs workgroups one after the other in ticket order:
+k_gs_partials, about 8 s per case here, so it stayed in the CPU suite).  The emulation runs workgroups one after the other in ticket order:
 a tile's nearest predecessor always holds a prefix of the current epoch, so the look-back never waits, never takes a second round of 64 words, never
 meets a stale word, and a misaligned 16-byte access does not trap.  Those are what the GPU part is for.
 
@@ -21,7 +21,7 @@ import pytest
 from phaser_amd import _lib
 
 U32, U64 = np.uint32, np.uint64
-TILE = 4096                                # GS_CHUNK = SCAN_CHUNK
+TILE = 4096                                # GS_CHUNK
 BOUNDARY = 4 << 20                         # u32 sums: look-back below, three launches from here on
 MANY_CHUNKS = 1025 * TILE + 5              # more than 1,024 chunk sums: the one-block scan of the sums loops and carries
 OVER_64_TILES = 65 * TILE + 7
@@ -29,7 +29,7 @@ GUARD = {4: 0xA5A5A5A5, 8: 0xA5A5A5A5A5A5A5A5}
 EPOCH_NEAR_RESET = (1 << 30) - 4
 
 # (impl, input type, sum type, transform): every instantiation the library has
-U32_ALL = [(0, U32, U32, 0), (1, U32, U32, 0), (2, U32, U32, 0)]
+U32_ALL = [(1, U32, U32, 0), (2, U32, U32, 0)]
 COMBOS = U32_ALL + [(1, U64, U64, 0), (2, U64, U64, 0), (1, U32, U64, 0), (2, U32, U64, 0), (1, U32, U32, 1), (2, U32, U32, 1)]
 
 
@@ -168,7 +168,7 @@ def test_emu_status_words_over_a_sequence_of_scans_and_the_epoch_reset():
     status_word_sequence(emu_ctx)
 
 
-@pytest.mark.parametrize("impl", [0, 2])
+@pytest.mark.parametrize("impl", [2])
 def test_emu_scan_of_more_than_1024_chunks(impl):
     """the one-block scan of the chunk sums takes a second trip, carrying the first one's total"""
     x = np.random.default_rng(105).integers(0, 256, MANY_CHUNKS).astype(U32)
@@ -178,7 +178,8 @@ def test_emu_scan_of_more_than_1024_chunks(impl):
 def test_emu_scan_refuses_what_is_not_instantiated():
     ctx = emu_ctx()
     x32 = np.ones(8, dtype=U32); x64 = np.ones(8, dtype=U64)
-    assert device_scan(ctx, 0, x64, U64)[0] == _lib.PHZ_E_ARG            # scan_excl is u32 only
+    assert device_scan(ctx, 0, x32, U32)[0] == _lib.PHZ_E_ARG            # impl 0 (the older scan) is gone, whatever the types
+    assert device_scan(ctx, 0, x64, U64)[0] == _lib.PHZ_E_ARG
     assert device_scan(ctx, 0, x32, U64)[0] == _lib.PHZ_E_ARG
     assert device_scan(ctx, 1, x64, U64, transform=1)[0] == _lib.PHZ_E_ARG      # LabelWidth: u32 -> u32 only
     assert device_scan(ctx, 2, x32, U64, transform=1)[0] == _lib.PHZ_E_ARG
@@ -225,7 +226,7 @@ GPU_SIZES = [1, 4097, 64 * TILE - 1, 64 * TILE, 64 * TILE + 1, 1_000_003, BOUNDA
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("impl", [0, 1, 2])
+@pytest.mark.parametrize("impl", [1, 2])
 def test_gpu_scan_equals_cumsum(ctx, impl):
     """64 tiles and one either side (the look-back's second round of 64 words needs more than 64 tiles in flight), the dispatch boundary of impl 1, and
     more than 1,024 chunks"""
@@ -262,13 +263,13 @@ def test_gpu_scan_widening_and_transform(ctx, impl):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("impl", [0, 1, 2])
+@pytest.mark.parametrize("impl", [1, 2])
 def test_gpu_scan_with_skewed_base_pointers(ctx, impl):
     """base + k, as K_annot passes `tile_count + t0`: the 16-byte accesses must be taken only where the address is aligned"""
     for n in (4097, 1_000_003):
         x, ref = gpu_case(n, "bytes")
         for in_skew in range(4):
-            for out_skew in (range(4) if impl else (0,)):
+            for out_skew in range(4):
                 check(ctx, impl, x, U32, ref=ref, in_skew=in_skew, out_skew=out_skew)
 
 

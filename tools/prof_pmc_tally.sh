@@ -2,7 +2,7 @@
 # Runs ON THE GPU BOX: HBM traffic of the phasing pass of the bench workload (configs[2]), split into the K_tally family (phz_tally.hip) and the
 # device row stage (phz_rowsdev.hip): FETCH_SIZE and WRITE_SIZE in separate rocprofv3 --pmc passes (kernel trace only) of a bench run with
 # phasing passes.  Dispatches are attributed by their place in the stream: k_as_hist .. k_edge_final = tally, k_pair_keys .. the last row /
-# label / vcf kernel = rows (the shared scan / sort kernels of phz_sort.h go to the family whose section they run in).  Writes
+# label / vcf kernel = rows (the shared scan / sort kernels of phz_scan.h / phz_sort.h go to the family whose section they run in).  Writes
 # gpurun_out/<tag>/pmc_ktally_c3/ with a meta.json naming the kernel sources; bench.py reports the numbers only while those hashes match.
 # usage: tools/prof_pmc_tally.sh <tag>
 set -u
