@@ -15,6 +15,7 @@
  *                        :1594-1635 test_variant_connection's nine set intersections, :917-931 / :1086-1115 the
  *                        per-haplotype read lists of the block output loop (what SURVEY.md 8(b) calls phz_hap_counts)
  *   phz_components       phaser/phaser.py:1861-1882      build_haplotypes / :1985 build_haplotype_v3
+ *   phz_variant_links    phaser/phaser.py:1928-1949      generate_hap_network_all (the links of --output_network, :1127-1157)
  *
  * Deliberately NOT exported (SURVEY.md 8(b) suggested them):
  *   phz_load_variants    variant arrays travel with every call instead (6 B per SNP; nothing to keep resident between shards)
@@ -281,6 +282,23 @@ int phz_tally_fetch(phz_ctx *ctx, const phz_tally_out *out, int space);
  * per-variant haplotype counts of phaser/phaser.py:1196-1204 (a block's union over its variants is the read-set stage of phz_rowsdev_run).
  * counts[(variant * 2 + allele) * n_bams + bam]; n_counts must equal variants x 2 x BAMs of the last phz_tally. */
 int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, int space);
+
+/* Allele links among a set of variants, read from the pair cells of the resident tally (nothing is intersected again): what generate_hap_network_all
+ * (phaser/phaser.py:1928-1949) computes for the block of --output_network (:1127-1157), for ANY strictly ascending set `vars` of the joint variant space of the
+ * last phz_tally / phz_tally_import -- a haplotype block is only what the command line passes.  For every pair i < j of set members (local indices = positions
+ * in vars) that the tally paired, and (x, y) in (0,0), (0,1), (1,0), (1,1) with count = |S_i[x] & S_j[y]| > 0 (distinct QNAMEs over all BAMs): the direct row
+ * (i, j, count, x, y, inferred 0) and then the inferred row (i, j, count, 1 - x, 1 - y, inferred 1); pairs in (i, j) order.  The same rows on every run.
+ * rows_cap too small: PHZ_E_CAPACITY and *n_rows = the number of rows (nothing is written).  n_vars < 2: no row, no error.  PHZ_E_ARG with a message, the ctx
+ * staying usable: no resident tally; a tally imported without edge_cells; vars not strictly ascending or outside [0, nv).  vars and rows live in `space`. */
+typedef struct {
+    int32_t i, j;            /* positions in vars, i < j */
+    int32_t count;
+    uint8_t allele_i, allele_j, inferred, pad;
+} phz_link_rec;
+int phz_variant_links(phz_ctx *ctx, const int32_t *vars, int64_t n_vars, phz_link_rec *rows, int64_t rows_cap, int64_t *n_rows, int space);
+/* Stamp of the resident tally: the number of phz_tally / phz_tally_import calls on this ctx so far (0: none).  Whoever keeps results derived from one tally (the
+ * blocks of a pass) compares it before reading the resident arrays again: the device row stage does between its two stages, phaser_amd/network.py before the links. */
+int phz_tally_generation(phz_ctx *ctx, uint64_t *gen);
 
 /* Connected components of the variant graph restricted to edges with keep != 0: label[v] = smallest variant
  * index of v's component.  edge_a == edge_b == NULL: the edge list of the last phz_tally (n_edges must match).

@@ -225,6 +225,9 @@ class phz_gene_rows_in(C.Structure):
 
 PHZ_AS_BINS = 65536
 
+# phz_link_rec as a numpy record (16 bytes): positions i < j in the variant set, count, allele of i, allele of j, inferred flag
+LINK_DTYPE = [("i", "<i4"), ("j", "<i4"), ("count", "<i4"), ("allele_i", "u1"), ("allele_j", "u1"), ("inferred", "u1"), ("pad", "u1")]
+
 # every symbol include/phz.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "phz_version": (C.c_int, []),
@@ -257,6 +260,8 @@ SYMBOLS = {
                                   C.POINTER(phz_tally_sizes), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "phz_tally_fetch": (C.c_int, [C.c_void_p, C.POINTER(phz_tally_out), C.c_int]),
     "phz_hap_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "phz_variant_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]),
+    "phz_tally_generation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "phz_load_variants": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(phz_variants)]),
     "phz_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_bgzf_inflate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int)]),

@@ -185,6 +185,15 @@ int PhzMail::send() {
     return PHZ_OK;
 }
 
+// Which resident tally the ctx holds: the count of phz_tally / phz_tally_import calls so far (0 = none yet).  A caller that keeps something derived from one
+// tally (the blocks of a pass) compares the stamp before it reads the resident arrays again (phz_variant_links).
+extern "C" int phz_tally_generation(phz_ctx *ctx, uint64_t *gen) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || !gen) return PHZ_E_ARG;
+    *gen = ctx->tally_gen;
+    return PHZ_OK;
+}
+
 // Adopt results computed elsewhere as the resident tally of this ctx (see phz.h).  Arrays a caller leaves NULL stay unset; the device
 // row stage needs var_count, var_first, var_distinct, var_rank, edge_a / edge_b, edge_linked, edge_stats, rl_start, rl_qid and rl_list.
 extern "C" int phz_tally_import(phz_ctx *ctx, int64_t nv, int n_bams, const phz_tally_sizes *sz, const phz_tally_out *a, const uint32_t *rl_list, int space) {

@@ -37,6 +37,8 @@ enum PhzScratch {
     SC_INFLATE_LENS = 11,
     // K_annot (phz_annot_pairs): rows per tile, their exclusive scan, the scan's temporary, the records of one batch
     SC_ANNOT_COUNT = 0, SC_ANNOT_BASE = 1, SC_ANNOT_SCAN_TMP = 2, SC_ANNOT_OUT = 3,
+    // phz_variant_links: rows per edge of the range, their exclusive scan, the scan's temporary, edge range + verdict on the set
+    SC_LINK_COUNT = 0, SC_LINK_BASE = 1, SC_LINK_SCAN_TMP = 2, SC_LINK_HEAD = 3,
     SC_COUNT = 24
 };
 

@@ -1633,6 +1633,128 @@ extern "C" int phz_tally_fetch(phz_ctx *ctx, const phz_tally_out *out, int space
     return PHZ_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ phz_variant_links
+// Allele links among a set of variants, from the pair table the tally left in HBM (phaser.py:1928-1949 generate_hap_network_all: |read_set[v][x] & read_set[o][y]| for
+// every pair v < o of a block and x, y in {0, 1} -- cells 0, 1, 3, 4 of the pair's nine, the same deduplicated QNAME sets over all BAMs).  Nothing is intersected again:
+//   k_links_head    checks the set (strictly ascending, inside [0, nv)) and cuts the (a, b)-sorted edge list to the edges whose a lies in [vars[0], vars[n - 1]]
+//   k_links<false>  one thread per edge of that range: both endpoints looked up in the set (bisection), 2 rows per non-zero cell counted
+//   gscan_excl      counts -> offsets (and the total)
+//   k_links<true>   the same threads write their rows at the offsets: edge order (= (i, j) order: local order is index order), x, y, direct before inferred
+// Placement needs no atomics; the output is the same on every run.  One small launch per run that asks for it, untimed.
+namespace {
+// number of entries of the ascending array w[0, n) below key
+__device__ __forceinline__ int64_t links_lower_bound(const int32_t *w, int64_t n, int64_t key) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)w[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// head[0] / head[1]: the edge range [lo, hi); head[2] != 0: the set is not strictly ascending inside [0, nv) (zeroed by the driver)
+__global__ __launch_bounds__(256) void k_links_head(const int32_t *vars, int64_t n, int64_t nv, const int32_t *ea, int64_t ne, long long *head) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) {
+        const int32_t v = vars[t];
+        if (v < 0 || (int64_t)v >= nv || (t + 1 < n && vars[t + 1] <= v)) head[2] = 1;
+    }
+    if (t == 0) head[0] = links_lower_bound(ea, ne, (int64_t)vars[0]);
+    if (t == 1) head[1] = links_lower_bound(ea, ne, (int64_t)vars[n - 1] + 1);
+}
+template <bool FILL> __global__ __launch_bounds__(256) void k_links(const int32_t *vars, int64_t n, const int32_t *ea, const int32_t *eb, const int32_t *cells, int64_t e0,
+                                                                    int64_t m, uint32_t *count, const unsigned long long *base, phz_link_rec *rows, int64_t rows_cap) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const int64_t e = e0 + t;
+    const int32_t a = ea[e], b = eb[e];
+    const int64_t i = links_lower_bound(vars, n, a), j = links_lower_bound(vars, n, b);
+    const bool member = i < n && vars[i] == a && j < n && vars[j] == b;
+    int32_t c[4] = {0, 0, 0, 0};
+    if (member) { const int32_t *row = cells + e * 9; c[0] = row[0]; c[1] = row[1]; c[2] = row[3]; c[3] = row[4]; }
+    if (!FILL) {
+        count[t] = 2u * (uint32_t)((c[0] > 0) + (c[1] > 0) + (c[2] > 0) + (c[3] > 0));
+        return;
+    }
+    int64_t at = (int64_t)base[t];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (c[k] <= 0) continue;
+        if (at + 2 > rows_cap) return;                  // (the driver launches this pass only with room for every row)
+        const uint8_t x = (uint8_t)(k >> 1), y = (uint8_t)(k & 1);
+        phz_link_rec r;
+        r.i = (int32_t)i; r.j = (int32_t)j; r.count = c[k]; r.pad = 0;
+        r.allele_i = x; r.allele_j = y; r.inferred = 0; rows[at] = r;
+        r.allele_i = (uint8_t)(1 - x); r.allele_j = (uint8_t)(1 - y); r.inferred = 1; rows[at + 1] = r;
+        at += 2;
+    }
+}
+}  // namespace
+
+// The link rows of ANY strictly ascending set of variants of the resident tally (a haplotype block is only what the command line passes); see phz.h.
+// Host waits: one for the edge range and the verdict on the set, one for the row count, one for the rows of a PHZ_HOST caller.
+extern "C" int phz_variant_links(phz_ctx *ctx, const int32_t *vars, int64_t n_vars, phz_link_rec *rows, int64_t rows_cap, int64_t *n_rows, int space) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || !n_rows || n_vars < 0 || rows_cap < 0 || (n_vars && !vars) || (rows_cap && !rows)) return PHZ_E_ARG;
+    *n_rows = 0;
+    // ---- what is resident
+    auto &T = ctx->tally;
+    if (ctx->tally_gen == 0) return phz_fail(ctx, PHZ_E_ARG, "phz_variant_links: no resident tally (phz_tally or phz_tally_import first)");
+    if (T.n_edges && (!T.ea || !T.eb || !T.cells)) return phz_fail(ctx, PHZ_E_ARG, "phz_variant_links: the resident tally was imported without edge_cells (the pair cells are what the links are read from)");
+    if (space == PHZ_HOST)
+        for (int64_t k = 0; k < n_vars; k++)
+            if (vars[k] < 0 || vars[k] >= T.nv || (k && vars[k] <= vars[k - 1])) return phz_fail(ctx, PHZ_E_ARG, "phz_variant_links: vars must be strictly ascending inside [0, nv) of the resident tally");
+    if (n_vars < 2 && space == PHZ_HOST) return PHZ_OK;          // no pair, no row (a PHZ_DEVICE set is still checked below)
+    if (n_vars == 0) return PHZ_OK;
+    PHZ_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t sm = ctx->stream;
+    Staging st(ctx);
+    const int32_t *d_vars; phz_link_rec *d_rows;
+    if (int s = st.in(vars, (size_t)n_vars, space, &d_vars)) return s;
+    if (int s = st.out(rows, (size_t)rows_cap, space, &d_rows)) return s;
+    // ---- the set checked on the device, the edge list cut to its range                                      WAIT
+    DevBuf *S = ctx->scratch;
+    if (int s = phz_reserve(ctx, S[SC_LINK_HEAD], 3 * sizeof(long long))) return s;
+    long long *head = (long long *)S[SC_LINK_HEAD].p;
+    PHZ_HIP(ctx, hipMemsetAsync(head, 0, 3 * sizeof(long long), sm));
+    hipLaunchKernelGGL(k_links_head, dim3(nblk(n_vars)), dim3(256), 0, sm, d_vars, n_vars, T.nv, (const int32_t *)T.ea, T.n_edges, head);
+    PHZ_HIP(ctx, hipGetLastError());
+    int64_t e0, m;
+    {
+        PhzMail mail(ctx);
+        const int m0 = mail.add(head, 3 * sizeof(long long));
+        if (int s = mail.send()) return s;
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        const long long *h = mail.at<long long>(m0);
+        if (h[2]) return phz_fail(ctx, PHZ_E_ARG, "phz_variant_links: vars must be strictly ascending inside [0, nv) of the resident tally");
+        e0 = h[0]; m = h[1] - h[0];
+    }
+    if (n_vars < 2 || m <= 0) return PHZ_OK;
+    if (e0 < 0 || e0 + m > T.n_edges) return phz_fail(ctx, PHZ_E_ARG, "phz_variant_links: edge range outside the resident list");
+    // ---- count, scan                                                                                         WAIT
+    if (int s = reserve_all(ctx, {{S[SC_LINK_COUNT], (size_t)m * 4}, {S[SC_LINK_BASE], ((size_t)m + 1) * 8}})) return s;
+    uint32_t *count = (uint32_t *)S[SC_LINK_COUNT].p;
+    unsigned long long *base = (unsigned long long *)S[SC_LINK_BASE].p;
+    hipLaunchKernelGGL(k_links<false>, dim3(nblk(m)), dim3(256), 0, sm, d_vars, n_vars, (const int32_t *)T.ea, (const int32_t *)T.eb, (const int32_t *)T.cells, e0, m, count,
+                       (const unsigned long long *)nullptr, (phz_link_rec *)nullptr, (int64_t)0);
+    PHZ_HIP(ctx, hipGetLastError());
+    if (int s = gscan_excl<uint32_t, unsigned long long>(ctx, count, base, m, S[SC_LINK_SCAN_TMP])) return s;
+    int64_t total;
+    {
+        PhzMail mail(ctx);
+        const int m0 = mail.add(base + m, 8);
+        if (int s = mail.send()) return s;
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        total = (int64_t)*mail.at<unsigned long long>(m0);
+    }
+    *n_rows = total;
+    if (total > rows_cap) return phz_fail(ctx, PHZ_E_CAPACITY, "phz_variant_links: rows_cap too small (n_rows holds the number of rows)");
+    if (total == 0) return PHZ_OK;
+    // ---- fill                                                                                                WAIT
+    hipLaunchKernelGGL(k_links<true>, dim3(nblk(m)), dim3(256), 0, sm, d_vars, n_vars, (const int32_t *)T.ea, (const int32_t *)T.eb, (const int32_t *)T.cells, e0, m,
+                       (uint32_t *)nullptr, (const unsigned long long *)base, d_rows, rows_cap);
+    PHZ_HIP(ctx, hipGetLastError());
+    if (space == PHZ_HOST) PHZ_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)total * sizeof(phz_link_rec), hipMemcpyDeviceToHost, sm));
+    PHZ_HIP(ctx, hipStreamSynchronize(sm));
+    return PHZ_OK;
+}
+
 // edge_a == edge_b == NULL: the edges of the last phz_tally, still resident in HBM (n_edges must match); keep[] lives in `space`
 extern "C" int phz_components(phz_ctx *ctx, int64_t nv, int64_t n_edges, const int32_t *edge_a, const int32_t *edge_b,
                               const uint8_t *keep, int32_t *label, int space) {

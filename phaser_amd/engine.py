@@ -404,6 +404,9 @@ class Engine:
              "fetched": False}
         if pair_stage is not None:
             G["pair_stage"] = pair_stage
+        gen = C.c_uint64(0)
+        self.ctx.check(self.lib.phz_tally_generation(self.ctx.h, C.byref(gen)))
+        G["gen"] = int(gen.value)          # which resident tally this pass owns (network.check_resident)
         self.stats["tally_call_s"] = self.stats.get("tally_call_s", 0.0) + t1 - t0
         return G
 
@@ -493,6 +496,7 @@ class Engine:
         noise = self.noise_from_counts(match, mism)
         t1 = _t.perf_counter()
         local = self._fragments(noise)
+        self._net_blocks = {c: local[c].get("vcf") for c in self.chrom_list} if (self.cfg.want_vcf or self.cfg.py_hash_order) else None      # per-block arrays of THIS rank's chromosomes (network())
         t2 = _t.perf_counter()
         frags = pdist.gather_fragments(local, getattr(self, "spool_dir", None), self.all_chroms)
         self.stats.update({"tally_s": t1 - t0, "fragments_s": t2 - t1})
@@ -534,6 +538,14 @@ class Engine:
         out = {k: b"".join(pdist.as_bytes(x) for x in v) for k, v in out.items()}
         pdist.cleanup_spool()
         return out if binary else {k: v.decode() for k, v in out.items()}
+
+    def network(self, variant_id: str, _links=None) -> Optional[dict]:
+        """--output_network for embedding callers (phaser.py:1127-1157), after finish(): {"links": bytes of <o>.network.links.txt, "nodes": bytes of
+        <o>.network.nodes.txt, "chrom", "variants", "records"} for the final haplotype block that holds the unique id `variant_id`, or None when the variant is in
+        no block of this rank's chromosomes (a singleton, an unknown id).  The counts come from the pair cells the tally left in HBM (phz_variant_links): the pass
+        must still be the context's resident one.  Needs Config.want_vcf (the per-block arrays); with Config.py_hash_order the nodes come in the reference's order."""
+        from . import network
+        return network.network(self, variant_id, _links=_links)
 
     def _fragments(self, noise: float) -> Dict[str, dict]:
         """Stage C for every owned chromosome: C1 = pair tests, pruning, components, ordering keys (numpy / scipy / GPU, the

@@ -3,8 +3,9 @@
 Same flags, defaults and output files as phaser/phaser.py:26-178 (`main`), :182-321 (`parse_sample`) and
 :378-1263 (`process_vcf`).  What differs is below the CLI: no samtools / bedtools / tabix subprocesses (BAM,
 BED and VCF are read in-process) and the seven multiprocessing stages are one `Engine` driving libphz.so.
-The phased VCF (`write_vcf`) is written as BGZF `<o>.vcf.gz` with its tabix index `<o>.vcf.gz.tbi`.  Not supported:
-`--process_slow`, `--output_network`.
+The phased VCF (`write_vcf`) is written as BGZF `<o>.vcf.gz` with its tabix index `<o>.vcf.gz.tbi`.  `--output_network VARIANT`
+writes `<o>.network.links.txt` / `<o>.network.nodes.txt` for the block that holds the variant (phaser_amd/network.py).  Not supported:
+`--process_slow`.
 
     python -m phaser_amd.phaser --vcf S.vcf.gz --bam a.bam,b.bam --sample S1 --mapq 255 --baseq 10 --paired_end 1 --o out
 """
@@ -143,8 +144,6 @@ def _main(argv, state):
         fatal_error("ID separator must not be ':' or blank. Please choose another separator that is not found in the contig names.")
     if args.process_slow != 0:
         fatal_error("--process_slow is not supported by this build (the GPU path holds all chromosomes; SURVEY.md section 2).")
-    if args.output_network != "":
-        fatal_error("--output_network is not supported by this build.")
     if args.py_hash_order and world > 1:
         # every rank sees the same arguments and stops HERE, before the first collective: nobody is left waiting in a barrier
         fatal_error("--py_hash_order 1 needs all chromosomes on one rank (run it without torch.distributed).")
@@ -342,6 +341,8 @@ def _main(argv, state):
                  id_separator=args.id_separator, unphased_vars=args.unphased_vars, gw_phase_method=args.gw_phase_method,
                  output_read_ids=args.output_read_ids, unique_ids=args.unique_ids, haplo_count_bam_exclude=excl, py_hash_order=args.py_hash_order,
                  include_indels=args.include_indels, host_threads=max(1, args.threads))
+    if args.output_network != "":
+        cfg.want_vcf = True            # the per-block arrays (the switch write_vcf and --py_hash_order set): the block of the variant is looked up in them
     if pre is not None:
         pre["ready"].wait()
     mapper0 = pre.get("mapper") if pre is not None else None
@@ -461,6 +462,16 @@ def _main(argv, state):
     mark("tally + pair tests + components + block phasing + rows")
     if os.environ.get("PHZ_TIMING"):
         sys.stderr.write("[phz timing]   finish: %s\n" % ", ".join("%s %.3f" % (k, v) for k, v in eng.stats.items()))
+    if args.output_network != "":
+        # phaser.py:1127-1157: the rank that owns the variant's chromosome has its block and the pair cells of its tally still in HBM: it writes the two files
+        # (all ranks share the node's file system, as for the spool files)
+        net = eng.network(args.output_network)
+        if net is not None:
+            pdist.write_files([(args.o + ".network.links.txt", [net["links"]]), (args.o + ".network.nodes.txt", [net["nodes"]])], threads=2)
+        found, _ = pdist.allreduce_counts(1 if net is not None else 0, 0)
+        if found == 0:
+            say("     variant %s is in no phased block: no network files written" % args.output_network)
+        mark("network of " + args.output_network)
     if files is not None:
         for line in eng.log[n_before:]:
             say(line)

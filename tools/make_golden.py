@@ -146,6 +146,9 @@ def run_pipeline(phaser, rvm, vcf_text, sams, outdir, capture_calls=True, haplo_
     res["log"] = log.getvalue()
     if ns.write_vcf == 1:
         res["vcf"] = open(prefix + ".vcf").read()
+    for suf in ["network.links", "network.nodes"]:          # --output_network: written only when the variant sits in a final block (phaser.py:1127-1157)
+        if os.path.exists(prefix + "." + suf + ".txt"):
+            res[suf] = open(prefix + "." + suf + ".txt").read()
     shutil.rmtree(work)
     return res, calls
 
@@ -743,7 +746,90 @@ def fx_expr_matrix(phaser, rvm):
         print("expr_matrix", order, len(files), "files ->", out_all.split("\n")[0].count("\t") - 3, "sample columns,", len(out_all.splitlines()) - 1, "rows")
 
 
-FIXTURES = {"sparse": fx_sparse, "kat": fx_kat, "mapper_small": fx_mapper_small, "mapper_unsorted": fx_mapper_unsorted, "pipeline": fx_pipeline, "c1": fx_c1, "write_vcf": fx_write_vcf, "write_vcf_more": fx_write_vcf_more, "indels": fx_indels, "options": fx_options, "gene_ae": fx_gene_ae, "expr_matrix": fx_expr_matrix, "blacklist_bed": fx_blacklist_bed}
+def _blocks_of(ase_text):
+    """haplotypic_counts.txt -> [unique-id list per block] in file order (one row per block and BAM: every block once)"""
+    out = []; seen = set()
+    for l in ase_text.split("\n")[1:]:
+        if l and l.split("\t")[3] not in seen:
+            seen.add(l.split("\t")[3]); out.append(l.split("\t")[3].split(","))
+    return out
+
+
+def _split_components(d):
+    """Blocks of a committed fixture that phase_v3 cut out of a larger connected component: the components of the surviving connections (the pairs of
+    variant_connections.txt whose p-value is not below the fixture's threshold) against the blocks of haplotypes.txt.  -> [blocks of one component]."""
+    gz = lambda n: gzip.open(os.path.join(d, "out.%s.txt.gz" % n), "rt").read()
+    parent = {}
+
+    def find(x):
+        while parent.setdefault(x, x) != x:
+            parent[x] = parent[parent[x]]; x = parent[x]
+        return x
+    for l in gz("variant_connections").split("\n")[1:]:
+        f = l.split("\t")
+        if len(f) >= 5 and not float(f[4]) < 0.01:
+            parent[find(f[0])] = find(f[1])
+    comp = {}
+    for blk in _blocks_of(gz("haplotypic_counts")):
+        if len(blk) > 1:
+            comp.setdefault(find(blk[0]), []).append(blk)
+    return [v for v in comp.values() if len(v) > 1]
+
+
+def fx_network(phaser, rvm):
+    """--output_network VARIANT (phaser.py:1127-1157, generate_hap_network_all :1928-1949): the committed inputs of existing fixtures run again with the option;
+    only <o>.network.links.txt / <o>.network.nodes.txt are kept (tests/golden/network/<case>.*.txt.gz + cases.json).  The five files of every rerun must be the
+    committed ones, byte for byte."""
+    d0 = os.path.join(GOLD, "network"); os.makedirs(d0, exist_ok=True)
+    gz = lambda p: gzip.open(p, "rt").read()
+
+    def inputs(fixture, bams, chroms):
+        d = os.path.join(GOLD, fixture)
+        return open(os.path.join(d, "in.vcf")).read(), {b + ".bam": {c: gz(os.path.join(d, "%s.%s.sam.gz" % (b, c))) for c in chroms} for b in bams}, d
+
+    def pick(fixture, d, singleton):
+        hap = gz(os.path.join(d, "out.haplotypic_counts.txt.gz"))
+        if fixture == "pipe_two":          # the largest block of the second chromosome (non-zero base in the joint variant space), middle variant
+            blk = max((b for b in _blocks_of(hap) if b[0].startswith("chr22_")), key=len)
+            return blk[len(blk) // 2]
+        if fixture == "pipe_noisy_b":      # a block phase_v3 cut out of a larger component: the second-largest piece of the component with the most pieces
+            pieces = max(_split_components(d), key=len)
+            blk = sorted(pieces, key=len)[-2] if len(pieces) > 1 else pieces[0]
+            return blk[0]
+        if fixture == "pipe_indel":        # a block that holds an indel allele; the variant asked for is the indel itself
+            is_indel = lambda u: len(u.split("_")[2]) != len(u.split("_")[3])
+            blk = max((b for b in _blocks_of(hap) if len(b) > 2 and any(is_indel(u) for u in b)), key=len)
+            return [u for u in blk if is_indel(u)][0]
+        if fixture == "pipe_one" and not singleton:          # the largest block (the sample the command-line tests build into a BAM)
+            blk = max(_blocks_of(hap), key=len)
+            return blk[-1]
+        if fixture == "pipe_one":          # a variant that ends as a singleton block
+            return [b for b in _blocks_of(hap) if len(b) == 1][0][0]
+
+    cases = {}
+    plan = [("two_chr22", "pipe_two", ("t1", "t2"), ("chr21", "chr22"), {}, None),
+            ("noisy_b_split", "pipe_noisy_b", ("n",), ("chr22",), {"max_block_size": json.load(open(os.path.join(GOLD, "pipe_noisy_b", "meta.json")))["max_block_size"]}, None),
+            ("one_block", "pipe_one", ("a",), ("chr22",), {}, None),
+            ("one_singleton", "pipe_one", ("a",), ("chr22",), {}, None),
+            ("one_unknown", "pipe_one", ("a",), ("chr22",), {}, "chr22_1_A_C"),
+            ("indel_block", "pipe_indel", ("i",), ("chr22",), {"include_indels": 1}, None)]
+    for name, fixture, bams, chroms, kw, vid in plan:
+        vcf, sams, d = inputs(fixture, bams, chroms)
+        vid = vid or pick(fixture, d, name == "one_singleton")
+        res, _ = run_pipeline(phaser, rvm, vcf, sams, d0, capture_calls=False, output_network=vid, **kw)
+        for k in ["allelic_counts", "variant_connections", "haplotypes", "haplotypic_counts", "allele_config"]:
+            assert res[k] == gz(os.path.join(d, "out.%s.txt.gz" % k)), (name, k)          # the option changes nothing else
+        wrote = "network.links" in res
+        assert wrote == (name not in ("one_singleton", "one_unknown")), (name, vid)
+        if wrote:
+            wgz(os.path.join(d0, name + ".links.txt.gz"), res["network.links"])
+            wgz(os.path.join(d0, name + ".nodes.txt.gz"), res["network.nodes"])
+        cases[name] = {"fixture": fixture, "bams": list(bams), "chroms": list(chroms), "options": kw, "variant": vid, "files": wrote}
+        print("network/%s: %s -> %s" % (name, vid, "%d link rows, %d nodes" % (res["network.links"].count("\n") - 1, res["network.nodes"].count("\n") - 1) if wrote else "no files"))
+    json.dump({"cases": cases}, open(os.path.join(d0, "cases.json"), "w"), indent=1)
+
+
+FIXTURES = {"network": fx_network, "sparse": fx_sparse, "kat": fx_kat, "mapper_small": fx_mapper_small, "mapper_unsorted": fx_mapper_unsorted, "pipeline": fx_pipeline, "c1": fx_c1, "write_vcf": fx_write_vcf, "write_vcf_more": fx_write_vcf_more, "indels": fx_indels, "options": fx_options, "gene_ae": fx_gene_ae, "expr_matrix": fx_expr_matrix, "blacklist_bed": fx_blacklist_bed}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
