@@ -16,6 +16,7 @@
  *                        per-haplotype read lists of the block output loop (what SURVEY.md 8(b) calls phz_hap_counts)
  *   phz_components       phaser/phaser.py:1861-1882      build_haplotypes / :1985 build_haplotype_v3
  *   phz_variant_links    phaser/phaser.py:1928-1949      generate_hap_network_all (the links of --output_network, :1127-1157)
+ *   phz_read_haplotypes  phaser/phaser.py:1086-1123      the read-id lists of --output_read_ids 1, as per-read votes (a, b) for all blocks at once
  *
  * Deliberately NOT exported (SURVEY.md 8(b) suggested them):
  *   phz_load_variants    variant arrays travel with every call instead (6 B per SNP; nothing to keep resident between shards)
@@ -299,6 +300,23 @@ int phz_variant_links(phz_ctx *ctx, const int32_t *vars, int64_t n_vars, phz_lin
 /* Stamp of the resident tally: the number of phz_tally / phz_tally_import calls on this ctx so far (0: none).  Whoever keeps results derived from one tally (the
  * blocks of a pass) compares it before reading the resident arrays again: the device row stage does between its two stages, phaser_amd/network.py before the links. */
 int phz_tally_generation(phz_ctx *ctx, uint64_t *gen);
+
+/* Which template votes for which haplotype of which block, from the read lists of the resident tally (rl_start / rl_qid / rl_list; nothing is tallied again).  The
+ * reference only lists the QNAMEs per side of a block (--output_read_ids 1, phaser/phaser.py:1086-1123, :1196-1217): no counts, and a read on both sides looks like
+ * two reads.  Block k of the caller's table is blk_var[blk_off[k] : blk_off[k+1]] (variant indices of the joint variant space of the last phz_tally /
+ * phz_tally_import), blk_hap[i] the allele index (0 / 1) haplotype A carries at blk_var[i]; every variant in at most one block, one-variant blocks allowed.
+ * var_skip[v] != 0 leaves a variant out of the vote (the haplotype-count blacklist, :1070), bam_skip[b] != 0 a BAM (--haplo_count_bam_exclude, :1049); NULL: none.
+ * One record for every (block, BAM, template id) with an entry in a read list of a voting block variant in a voting BAM: a = entries (kept call lines; the two mates
+ * of a template count twice, as in reads[idx], :1318) on alleles haplotype A carries, b = on the other allele.  Sorted by (block, bam, qid); block = the position
+ * in the caller's table, qid = the chromosome-local template id as stored in rl_qid.  The same records on every run.
+ * rows_cap too small: PHZ_E_CAPACITY and *n_rows = the number of rows (nothing is written).  n_blocks == 0: no row, no error.  PHZ_E_ARG with a message, the ctx
+ * staying usable: no resident tally; a tally imported without rl_start / rl_qid / rl_list; a variant outside [0, nv) or in two blocks; blk_off not ascending;
+ * blk_hap above 1 (PHZ_HOST arguments are checked before anything is launched, PHZ_DEVICE ones by a kernel whose verdict arrives with the row count).
+ * PHZ_E_UNSUPPORTED: (block, bam, qid, side) does not fit 64 bits; 2^30 read-list entries or more.  All arrays live in `space`. */
+typedef struct { int32_t block, bam, qid, a, b; } phz_readhap_rec;      /* 20 bytes */
+int phz_read_haplotypes(phz_ctx *ctx, int64_t n_blocks, const int64_t *blk_off /* [n_blocks+1] */, const int32_t *blk_var, const uint8_t *blk_hap,
+                        const uint8_t *var_skip /* [nv] or NULL */, const uint8_t *bam_skip /* [n_bams] or NULL */,
+                        phz_readhap_rec *rows, int64_t rows_cap, int64_t *n_rows, int space);
 
 /* Connected components of the variant graph restricted to edges with keep != 0: label[v] = smallest variant
  * index of v's component.  edge_a == edge_b == NULL: the edge list of the last phz_tally (n_edges must match).

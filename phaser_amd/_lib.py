@@ -228,6 +228,9 @@ PHZ_AS_BINS = 65536
 # phz_link_rec as a numpy record (16 bytes): positions i < j in the variant set, count, allele of i, allele of j, inferred flag
 LINK_DTYPE = [("i", "<i4"), ("j", "<i4"), ("count", "<i4"), ("allele_i", "u1"), ("allele_j", "u1"), ("inferred", "u1"), ("pad", "u1")]
 
+# phz_readhap_rec as a numpy record (20 bytes): position of the block in the caller's table, BAM, chromosome-local template id, entries on haplotype A's alleles, on the other
+READHAP_DTYPE = [("block", "<i4"), ("bam", "<i4"), ("qid", "<i4"), ("a", "<i4"), ("b", "<i4")]
+
 # every symbol include/phz.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "phz_version": (C.c_int, []),
@@ -262,6 +265,7 @@ SYMBOLS = {
     "phz_hap_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "phz_variant_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]),
     "phz_tally_generation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "phz_read_haplotypes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]),
     "phz_load_variants": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(phz_variants)]),
     "phz_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_bgzf_inflate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int)]),

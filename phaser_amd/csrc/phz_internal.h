@@ -39,6 +39,10 @@ enum PhzScratch {
     SC_ANNOT_COUNT = 0, SC_ANNOT_BASE = 1, SC_ANNOT_SCAN_TMP = 2, SC_ANNOT_OUT = 3,
     // phz_variant_links: rows per edge of the range, their exclusive scan, the scan's temporary, edge range + verdict on the set
     SC_LINK_COUNT = 0, SC_LINK_BASE = 1, SC_LINK_SCAN_TMP = 2, SC_LINK_HEAD = 3,
+    // phz_read_haplotypes: verdict on the block table, block + side per variant, the two key buffers of the sort (the free one then holds the run list) and its
+    // value bytes, survivors per workgroup + scan, (runs, rows) per workgroup + scan, the sort's digit table, the scans' temporary
+    SC_RH_FLAG = 0, SC_RH_VBLK = 1, SC_RH_VSIDE = 2, SC_RH_KEY0 = 3, SC_RH_KEY1 = 4, SC_RH_VAL0 = 5, SC_RH_VAL1 = 6, SC_RH_LIVE_COUNT = 7, SC_RH_LIVE_BASE = 8,
+    SC_RH_RUN_COUNT = 9, SC_RH_RUN_BASE = 10, SC_RH_SORT_COUNT = 11, SC_RH_SCAN_TMP = 12,
     SC_COUNT = 24
 };
 

@@ -1755,6 +1755,240 @@ extern "C" int phz_variant_links(phz_ctx *ctx, const int32_t *vars, int64_t n_va
     return PHZ_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ phz_read_haplotypes
+// Which template votes for which haplotype of which block: per (block, BAM, QNAME id) the number of read-list entries on alleles haplotype A carries and on the
+// other allele, over ALL blocks of the caller's table at once, from the read lists the tally left in HBM (rl_list / rl_qid: one entry per kept ref / alt line).
+//   k_rh_head      the block offsets checked (ascending, not below 0, not more slots than variants)
+//   k_rh_scatter   one thread per block-variant slot: vblk[v] = block ordinal (-1: in no block, -2: in a block but left out of the vote), vside[v] = allele on
+//                  haplotype A; the slot's block by bisection of the offsets; a second writer to vblk[v] = a variant in two blocks
+//   k_rh_keys      one thread per read-list entry: key = block | BAM | QNAME id | side (bit 0: 0 = the allele haplotype A carries).  The entries are partitioned:
+//                  survivors first, in entry order, the dropped ones behind them with a key above every block (in-wave rank from a ballot, the workgroups'
+//                  counts through gscan_excl, the same threads fill) -- the number of survivors never visits the host, the sort takes all n_rl keys
+//   radix sort     over the significant bits of the key
+//   k_rh_runs      heads of full-key runs compacted into a position list (the same count / scan / fill; the scan carries runs and rows in one 64-bit sum); a
+//                  head that also starts a new (block, BAM, QNAME id) knows its row
+//   k_rh_rows      one thread per run that starts a row: its length and the length of the next run when that one has the same (block, BAM, QNAME id) -- both are
+//                  differences of neighbouring list entries, so no thread walks a run whatever its length
+// Host waits: one for the verdict on the arguments and the row count, one for the rows.  Every run gives the same records.  Untimed.
+namespace {
+enum { RH_F_OFF = 0, RH_F_RANGE = 1, RH_F_TWICE = 2, RH_F_HAP = 3 };          // words of the verdict block (zeroed by the driver)
+__global__ __launch_bounds__(256) void k_rh_head(const int64_t *blk_off, int64_t n_blocks, int64_t nv, uint32_t *flag) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k > n_blocks) return;
+    const int64_t o = blk_off[k];
+    if (o < 0 || (k < n_blocks && blk_off[k + 1] < o)) flag[RH_F_OFF] = 1;
+    if (k == 0 && blk_off[n_blocks] - o > nv) flag[RH_F_TWICE] = 1;          // more slots than variants: some variant is there twice
+}
+__global__ __launch_bounds__(256) void k_rh_scatter(const int64_t *blk_off, int64_t n_blocks, const int32_t *blk_var, const uint8_t *blk_hap, const uint8_t *var_skip, int64_t nv,
+                                                    int32_t *vblk, uint8_t *vside, uint32_t *flag) {
+    if (flag[RH_F_OFF] | flag[RH_F_TWICE]) return;          // offsets that say nothing about the slot arrays: those are not read
+    const int64_t s = blk_off[0] + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= blk_off[n_blocks]) return;
+    int64_t lo = 0, hi = n_blocks;                           // the last block that starts at or before s (empty blocks share their offset with the next one)
+    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (blk_off[mid] <= s) lo = mid; else hi = mid; }
+    const int32_t v = blk_var[s];
+    const uint8_t h = blk_hap[s];
+    if (v < 0 || (int64_t)v >= nv) { flag[RH_F_RANGE] = 1; return; }
+    if (h > 1) { flag[RH_F_HAP] = 1; return; }
+    const int32_t mine = var_skip && var_skip[v] ? -2 : (int32_t)lo;
+    if (atomicCAS(&vblk[v], -1, mine) != -1) flag[RH_F_TWICE] = 1; else vside[v] = h;
+}
+// place of a live thread among the live threads of its workgroup of 256 (ballot inside the wave, the four waves' counts in s_w), *total = their number; every
+// thread of the workgroup calls it
+__device__ __forceinline__ uint32_t rh_wg_rank(bool live, uint32_t *s_w, uint32_t *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(live ? 1 : 0);
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0;
+    for (int w = 0; w < wave; w++) before += s_w[w];
+    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return before + (uint32_t)__popcll(m & below);
+}
+struct RhKeys {
+    const uint32_t *rl_list; const int32_t *rl_qid; int64_t n, nv; uint32_t nb;
+    const int32_t *vblk; const uint8_t *vside, *bam_skip; const uint32_t *flag;
+    int bam_shift, blk_shift; unsigned long long pad;          // pad: the key of a dropped entry (block field = n_blocks)
+};
+template <bool FILL> __global__ __launch_bounds__(256) void k_rh_keys(RhKeys a, uint32_t *wg_count, const uint32_t *wg_base, unsigned long long *keys) {
+    __shared__ uint32_t s_w[4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool live = false;
+    unsigned long long key = a.pad;
+    if (i < a.n && !(a.flag[RH_F_OFF] | a.flag[RH_F_RANGE] | a.flag[RH_F_TWICE] | a.flag[RH_F_HAP])) {
+        const uint32_t e = a.rl_list[i], bam = e % a.nb, va = e / a.nb;
+        const int64_t v = (int64_t)(va >> 1);
+        const int32_t k = v < a.nv ? a.vblk[v] : -1;
+        if (k >= 0 && !(a.bam_skip && a.bam_skip[bam])) {
+            live = true;
+            key = ((unsigned long long)(uint32_t)k << a.blk_shift) | ((unsigned long long)bam << a.bam_shift) | ((unsigned long long)(uint32_t)a.rl_qid[i] << 1) |
+                  (unsigned long long)((va & 1u) != (uint32_t)a.vside[v]);
+        }
+    }
+    uint32_t total;
+    const uint32_t rank = rh_wg_rank(live, s_w, &total);
+    if (!FILL) { if (threadIdx.x == 0) wg_count[blockIdx.x] = total; return; }
+    if (i >= a.n) return;
+    const int64_t m = (int64_t)wg_base[gridDim.x], before = (int64_t)wg_base[blockIdx.x] + rank;          // survivors in all / in front of this entry
+    keys[live ? before : m + (i - before)] = key;
+}
+// counts and bases: runs in the high half, rows in the low half of one 64-bit sum (both below 2^30)
+template <bool FILL> __global__ __launch_bounds__(256) void k_rh_runs(const unsigned long long *keys, const uint32_t *n_live, unsigned long long *wg_count, const unsigned long long *wg_base,
+                                                                      uint32_t *run_pos, int32_t *run_row) {
+    __shared__ uint32_t s_run[4], s_row[4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < (int64_t)*n_live;
+    const unsigned long long key = in ? keys[i] : 0ull, prev = in && i > 0 ? keys[i - 1] : 0ull;
+    const bool run_head = in && (i == 0 || key != prev), row_head = in && (i == 0 || (key >> 1) != (prev >> 1));
+    uint32_t runs, rows;
+    const uint32_t run_rank = rh_wg_rank(run_head, s_run, &runs), row_rank = rh_wg_rank(row_head, s_row, &rows);
+    if (!FILL) { if (threadIdx.x == 0) wg_count[blockIdx.x] = ((unsigned long long)runs << 32) | rows; return; }
+    if (!run_head) return;
+    const unsigned long long base = wg_base[blockIdx.x];
+    const uint32_t r = (uint32_t)(base >> 32) + run_rank;
+    run_pos[r] = (uint32_t)i;
+    run_row[r] = row_head ? (int32_t)((uint32_t)base + row_rank) : -1;
+}
+__global__ __launch_bounds__(256) void k_rh_rows(const unsigned long long *keys, const uint32_t *n_live, const unsigned long long *totals, const uint32_t *run_pos, const int32_t *run_row,
+                                                 int bam_shift, int blk_shift, phz_readhap_rec *rows, int64_t rows_cap) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x, n_runs = (int64_t)(*totals >> 32);
+    if (r >= n_runs) return;
+    const int64_t row = run_row[r];
+    if (row < 0 || row >= rows_cap) return;                  // (the driver launches this kernel only with room for every row)
+    const uint32_t m = *n_live, p0 = run_pos[r], p1 = r + 1 < n_runs ? run_pos[r + 1] : m;
+    const unsigned long long key = keys[p0];
+    int32_t a = 0, b = 0;
+    if (key & 1ull) b = (int32_t)(p1 - p0);
+    else {
+        a = (int32_t)(p1 - p0);
+        if (r + 1 < n_runs && (keys[p1] >> 1) == (key >> 1)) b = (int32_t)((r + 2 < n_runs ? run_pos[r + 2] : m) - p1);
+    }
+    phz_readhap_rec rec;
+    rec.block = (int32_t)(key >> blk_shift); rec.bam = (int32_t)((key >> bam_shift) & ((1ull << (blk_shift - bam_shift)) - 1ull)); rec.qid = (int32_t)(uint32_t)(key >> 1);
+    rec.a = a; rec.b = b;
+    rows[row] = rec;
+}
+const char *rh_verdict(const uint32_t *f) {
+    if (f[RH_F_OFF]) return "phz_read_haplotypes: blk_off must ascend from a value not below 0";
+    if (f[RH_F_RANGE]) return "phz_read_haplotypes: a block variant outside [0, nv) of the resident tally";
+    if (f[RH_F_HAP]) return "phz_read_haplotypes: blk_hap holds a value above 1";
+    if (f[RH_F_TWICE]) return "phz_read_haplotypes: a variant in two blocks (or twice in one)";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int phz_read_haplotypes(phz_ctx *ctx, int64_t n_blocks, const int64_t *blk_off, const int32_t *blk_var, const uint8_t *blk_hap, const uint8_t *var_skip,
+                                   const uint8_t *bam_skip, phz_readhap_rec *rows, int64_t rows_cap, int64_t *n_rows, int space) {
+    PhzEnter phz_guard_(ctx);
+    if (!ctx || !n_rows || n_blocks < 0 || rows_cap < 0 || (n_blocks && !blk_off) || (rows_cap && !rows)) return PHZ_E_ARG;
+    *n_rows = 0;
+    // ---- what is resident
+    auto &T = ctx->tally;
+    if (ctx->tally_gen == 0) return phz_fail(ctx, PHZ_E_ARG, "phz_read_haplotypes: no resident tally (phz_tally or phz_tally_import first)");
+    if (!T.rl_start || !T.rl_qid || !T.rl_list)
+        return phz_fail(ctx, PHZ_E_ARG, "phz_read_haplotypes: the resident tally was imported without its read lists (rl_start, rl_qid and rl_list are what the votes are read from)");
+    // ---- arguments a host caller hands over: checked before anything is launched
+    const int64_t nv = T.nv, n_rl = T.n_rl;
+    int64_t n_slots = nv;                                    // threads of the scatter (a PHZ_DEVICE table has at most one slot per variant, or the head kernel refuses it)
+    if (space == PHZ_HOST && n_blocks) {
+        uint32_t f[4] = {0, 0, 0, 0};
+        for (int64_t k = 0; k <= n_blocks; k++)
+            if (blk_off[k] < 0 || (k < n_blocks && blk_off[k + 1] < blk_off[k])) f[RH_F_OFF] = 1;
+        if (!f[RH_F_OFF]) {
+            n_slots = blk_off[n_blocks] - blk_off[0];
+            if (n_slots && (!blk_var || !blk_hap)) return PHZ_E_ARG;
+            std::vector<uint8_t> seen((size_t)nv, 0);
+            for (int64_t s = blk_off[0]; s < blk_off[n_blocks]; s++) {
+                const int32_t v = blk_var[s];
+                if (v < 0 || v >= nv) { f[RH_F_RANGE] = 1; continue; }
+                if (blk_hap[s] > 1) f[RH_F_HAP] = 1;
+                if (seen[(size_t)v]) f[RH_F_TWICE] = 1;
+                seen[(size_t)v] = 1;
+            }
+        }
+        if (const char *why = rh_verdict(f)) return phz_fail(ctx, PHZ_E_ARG, why);
+    }
+    if (n_blocks == 0) return PHZ_OK;
+    if (space == PHZ_DEVICE && (!blk_var || !blk_hap)) return PHZ_E_ARG;
+    // ---- the key: block | BAM | QNAME id (32 bits as stored) | side
+    const int bam_shift = 33, bam_bits = bits_for((uint64_t)(T.nb > 1 ? T.nb - 1 : 1)), blk_shift = bam_shift + bam_bits, blk_bits = bits_for((uint64_t)n_blocks);
+    if (blk_shift + blk_bits > 64) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "phz_read_haplotypes: (block, bam, qid, side) does not fit a 64-bit key");
+    if (n_rl >= (1ll << 30)) return phz_fail(ctx, PHZ_E_UNSUPPORTED, "phz_read_haplotypes: 2^30 read-list entries or more (the device sort takes fewer)");
+    PHZ_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t sm = ctx->stream;
+    Staging st(ctx);
+    const int64_t *d_off; const int32_t *d_var; const uint8_t *d_hap, *d_vskip, *d_bskip; phz_readhap_rec *d_rows;
+    const size_t host_slots = space == PHZ_HOST ? (size_t)(blk_off[0] + n_slots) : 0;          // (the device copy keeps the caller's slot numbers)
+    if (int s = st.in(blk_off, (size_t)n_blocks + 1, space, &d_off)) return s;
+    if (int s = st.in(blk_var, host_slots, space, &d_var)) return s;
+    if (int s = st.in(blk_hap, host_slots, space, &d_hap)) return s;
+    if (int s = st.in(var_skip, (size_t)nv, space, &d_vskip)) return s;
+    if (int s = st.in(bam_skip, (size_t)T.nb, space, &d_bskip)) return s;
+    if (int s = st.out(rows, (size_t)rows_cap, space, &d_rows)) return s;
+    // ---- scatter: the block and the side of every variant
+    DevBuf *S = ctx->scratch;
+    const int64_t nwg = (n_rl + 255) / 256;
+    if (int s = reserve_all(ctx, {{S[SC_RH_FLAG], 4 * sizeof(uint32_t)}, {S[SC_RH_VBLK], (size_t)(nv ? nv : 1) * 4}, {S[SC_RH_VSIDE], (size_t)(nv ? nv : 1)},
+                                  {S[SC_RH_KEY0], (size_t)(n_rl ? n_rl : 1) * 8}, {S[SC_RH_KEY1], (size_t)(n_rl ? n_rl : 1) * 8}, {S[SC_RH_VAL0], (size_t)(n_rl ? n_rl : 1)},
+                                  {S[SC_RH_VAL1], (size_t)(n_rl ? n_rl : 1)}, {S[SC_RH_LIVE_COUNT], (size_t)(nwg ? nwg : 1) * 4}, {S[SC_RH_LIVE_BASE], ((size_t)nwg + 1) * 4},
+                                  {S[SC_RH_RUN_COUNT], (size_t)(nwg ? nwg : 1) * 8}, {S[SC_RH_RUN_BASE], ((size_t)nwg + 1) * 8}})) return s;
+    uint32_t *flag = (uint32_t *)S[SC_RH_FLAG].p;
+    int32_t *vblk = (int32_t *)S[SC_RH_VBLK].p; uint8_t *vside = (uint8_t *)S[SC_RH_VSIDE].p;
+    PHZ_HIP(ctx, hipMemsetAsync(flag, 0, 4 * sizeof(uint32_t), sm));
+    if (nv) { PHZ_HIP(ctx, hipMemsetAsync(vblk, 0xFF, (size_t)nv * 4, sm)); PHZ_HIP(ctx, hipMemsetAsync(vside, 0, (size_t)nv, sm)); }
+    hipLaunchKernelGGL(k_rh_head, dim3(nblk(n_blocks + 1)), dim3(256), 0, sm, d_off, n_blocks, nv, flag);
+    if (n_slots) hipLaunchKernelGGL(k_rh_scatter, dim3(nblk(n_slots)), dim3(256), 0, sm, d_off, n_blocks, d_var, d_hap, d_vskip, nv, vblk, vside, flag);
+    PHZ_HIP(ctx, hipGetLastError());
+    // ---- keys of the surviving entries, sorted; heads of runs, rows counted                                   WAIT
+    unsigned long long *keys = (unsigned long long *)S[SC_RH_KEY0].p, *other = (unsigned long long *)S[SC_RH_KEY1].p;
+    uint32_t *live_count = (uint32_t *)S[SC_RH_LIVE_COUNT].p, *live_base = (uint32_t *)S[SC_RH_LIVE_BASE].p;
+    unsigned long long *run_count = (unsigned long long *)S[SC_RH_RUN_COUNT].p, *run_base = (unsigned long long *)S[SC_RH_RUN_BASE].p;
+    uint32_t *run_pos = nullptr; int32_t *run_row = nullptr;
+    if (n_rl) {
+        RhKeys a;
+        a.rl_list = T.rl_list; a.rl_qid = T.rl_qid; a.n = n_rl; a.nv = nv; a.nb = (uint32_t)T.nb; a.vblk = vblk; a.vside = vside; a.bam_skip = d_bskip; a.flag = flag;
+        a.bam_shift = bam_shift; a.blk_shift = blk_shift; a.pad = (unsigned long long)n_blocks << blk_shift;
+        hipLaunchKernelGGL(k_rh_keys<false>, dim3((unsigned)nwg), dim3(256), 0, sm, a, live_count, (const uint32_t *)nullptr, (unsigned long long *)nullptr);
+        PHZ_HIP(ctx, hipGetLastError());
+        if (int s = gscan_excl<uint32_t, uint32_t>(ctx, live_count, live_base, nwg, S[SC_RH_SCAN_TMP])) return s;
+        hipLaunchKernelGGL(k_rh_keys<true>, dim3((unsigned)nwg), dim3(256), 0, sm, a, (uint32_t *)nullptr, (const uint32_t *)live_base, keys);
+        PHZ_HIP(ctx, hipGetLastError());
+        const int range[1][2] = {{0, blk_shift + blk_bits}};
+        int where = 0;
+        if (int s = radix_sort_ranges<unsigned long long, uint8_t>(ctx, keys, other, (uint8_t *)S[SC_RH_VAL0].p, (uint8_t *)S[SC_RH_VAL1].p, n_rl, range, 1, S[SC_RH_SORT_COUNT],
+                                                                     S[SC_RH_SCAN_TMP], &where)) return s;
+        if (where) std::swap(keys, other);
+        run_pos = (uint32_t *)other; run_row = (int32_t *)(run_pos + n_rl);          // the sort's other buffer is free again: 8 bytes per entry, as the two lists need
+        hipLaunchKernelGGL(k_rh_runs<false>, dim3((unsigned)nwg), dim3(256), 0, sm, (const unsigned long long *)keys, (const uint32_t *)(live_base + nwg), run_count,
+                           (const unsigned long long *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr);
+        PHZ_HIP(ctx, hipGetLastError());
+        if (int s = gscan_excl<unsigned long long, unsigned long long>(ctx, run_count, run_base, nwg, S[SC_RH_SCAN_TMP])) return s;
+        hipLaunchKernelGGL(k_rh_runs<true>, dim3((unsigned)nwg), dim3(256), 0, sm, (const unsigned long long *)keys, (const uint32_t *)(live_base + nwg), (unsigned long long *)nullptr,
+                           (const unsigned long long *)run_base, run_pos, run_row);
+        PHZ_HIP(ctx, hipGetLastError());
+    }
+    int64_t n_runs = 0, total = 0;
+    {
+        PhzMail mail(ctx);
+        const int m0 = mail.add(flag, 4 * sizeof(uint32_t)), m1 = n_rl ? mail.add(run_base + nwg, 8) : -1;
+        if (int s = mail.send()) return s;
+        PHZ_HIP(ctx, hipStreamSynchronize(sm));
+        if (const char *why = rh_verdict(mail.at<uint32_t>(m0))) return phz_fail(ctx, PHZ_E_ARG, why);
+        if (n_rl) { const unsigned long long t = *mail.at<unsigned long long>(m1); n_runs = (int64_t)(t >> 32); total = (int64_t)(t & 0xFFFFFFFFull); }
+    }
+    *n_rows = total;
+    if (total > rows_cap) return phz_fail(ctx, PHZ_E_CAPACITY, "phz_read_haplotypes: rows_cap too small (n_rows holds the number of rows)");
+    if (total == 0) return PHZ_OK;
+    // ---- one record per row, from the run list                                                               WAIT
+    hipLaunchKernelGGL(k_rh_rows, dim3(nblk(n_runs)), dim3(256), 0, sm, (const unsigned long long *)keys, (const uint32_t *)(live_base + nwg), (const unsigned long long *)(run_base + nwg),
+                       (const uint32_t *)run_pos, (const int32_t *)run_row, bam_shift, blk_shift, d_rows, rows_cap);
+    PHZ_HIP(ctx, hipGetLastError());
+    if (space == PHZ_HOST) PHZ_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)total * sizeof(phz_readhap_rec), hipMemcpyDeviceToHost, sm));
+    PHZ_HIP(ctx, hipStreamSynchronize(sm));
+    return PHZ_OK;
+}
+
 // edge_a == edge_b == NULL: the edges of the last phz_tally, still resident in HBM (n_edges must match); keep[] lives in `space`
 extern "C" int phz_components(phz_ctx *ctx, int64_t nv, int64_t n_edges, const int32_t *edge_a, const int32_t *edge_b,
                               const uint8_t *keep, int32_t *label, int space) {

@@ -497,6 +497,7 @@ class Engine:
         t1 = _t.perf_counter()
         local = self._fragments(noise)
         self._net_blocks = {c: local[c].get("vcf") for c in self.chrom_list} if (self.cfg.want_vcf or self.cfg.py_hash_order) else None      # per-block arrays of THIS rank's chromosomes (network())
+        self._net_order = block_chrom_order(local, self.chrom_list)          # ... in the order the block files list them (read_haplotypes())
         t2 = _t.perf_counter()
         frags = pdist.gather_fragments(local, getattr(self, "spool_dir", None), self.all_chroms)
         self.stats.update({"tally_s": t1 - t0, "fragments_s": t2 - t1})
@@ -546,6 +547,17 @@ class Engine:
         must still be the context's resident one.  Needs Config.want_vcf (the per-block arrays); with Config.py_hash_order the nodes come in the reference's order."""
         from . import network
         return network.network(self, variant_id, _links=_links)
+
+    def read_haplotypes(self, _launch=None) -> dict:
+        """Which read belongs to which haplotype of which block, after finish(): {"records": one (block, bam, qid, a, b) per template with a kept call line on a
+        voting variant of the block in a voting BAM (readhap.READHAP_DTYPE; a / b = its lines on haplotype A's alleles / on the other ones), "text": bytes of
+        <o>.read_haplotypes.txt, "blocks": the block table the records index (readhap.block_table: the blocks in haplotypic_counts order, then -- with
+        unphased_vars -- every variant in no block as a block of its own)}.  The votes come from the read lists the tally left in HBM (phz_read_haplotypes): the pass
+        must still be the context's resident one.  Needs Config.want_vcf (the per-block arrays) and, for the text, the QNAME tables (add_shard(..., qnames))."""
+        from . import readhap
+        table = readhap.block_table(self)
+        rec = readhap.records(self, _launch=_launch, table=table)
+        return {"records": rec, "text": readhap.text(self, rec, table=table), "blocks": table}
 
     def _fragments(self, noise: float) -> Dict[str, dict]:
         """Stage C for every owned chromosome: C1 = pair tests, pruning, components, ordering keys (numpy / scipy / GPU, the

@@ -4,8 +4,9 @@ Same flags, defaults and output files as phaser/phaser.py:26-178 (`main`), :182-
 :378-1263 (`process_vcf`).  What differs is below the CLI: no samtools / bedtools / tabix subprocesses (BAM,
 BED and VCF are read in-process) and the seven multiprocessing stages are one `Engine` driving libphz.so.
 The phased VCF (`write_vcf`) is written as BGZF `<o>.vcf.gz` with its tabix index `<o>.vcf.gz.tbi`.  `--output_network VARIANT`
-writes `<o>.network.links.txt` / `<o>.network.nodes.txt` for the block that holds the variant (phaser_amd/network.py).  Not supported:
-`--process_slow`.
+writes `<o>.network.links.txt` / `<o>.network.nodes.txt` for the block that holds the variant (phaser_amd/network.py).  `--output_read_haplotypes 1`
+(not an option of the reference) writes `<o>.read_haplotypes.txt`: per (block, BAM, read) its call lines on haplotype A's alleles and on the other ones
+(phaser_amd/readhap.py).  Not supported: `--process_slow`.
 
     python -m phaser_amd.phaser --vcf S.vcf.gz --bam a.bam,b.bam --sample S1 --mapq 255 --baseq 10 --paired_end 1 --o out
 """
@@ -79,6 +80,9 @@ def build_parser():
                         "in libphz: works under any Python, costs seconds at whole-genome scale; PHZ_PYORDER_PYTHON=1 selects the pure-Python twin)")
     p.add_argument("--id_separator", default="_")
     p.add_argument("--output_network", default="")
+    p.add_argument("--output_read_haplotypes", type=int, default=0,
+                   help="1: also write <o>.read_haplotypes.txt -- per (block, BAM, read) the number of its call lines on haplotype A's alleles and on the other "
+                        "ones, and the haplotype they vote for (not an option of the reference; one rank only)")
     p.add_argument("--process_slow", type=int, default=0, required=False)
     return p
 
@@ -147,6 +151,9 @@ def _main(argv, state):
     if args.py_hash_order and world > 1:
         # every rank sees the same arguments and stops HERE, before the first collective: nobody is left waiting in a barrier
         fatal_error("--py_hash_order 1 needs all chromosomes on one rank (run it without torch.distributed).")
+    if args.output_read_haplotypes and world > 1:
+        # likewise on every rank, before the first collective
+        fatal_error("--output_read_haplotypes 1 needs all chromosomes on one rank (run it without torch.distributed).")
     if not os.path.isfile(args.vcf):
         fatal_error("VCF file does not exist.")
     for xfile in [args.blacklist, args.haplo_count_blacklist]:
@@ -341,7 +348,7 @@ def _main(argv, state):
                  id_separator=args.id_separator, unphased_vars=args.unphased_vars, gw_phase_method=args.gw_phase_method,
                  output_read_ids=args.output_read_ids, unique_ids=args.unique_ids, haplo_count_bam_exclude=excl, py_hash_order=args.py_hash_order,
                  include_indels=args.include_indels, host_threads=max(1, args.threads))
-    if args.output_network != "":
+    if args.output_network != "" or args.output_read_haplotypes == 1:
         cfg.want_vcf = True            # the per-block arrays (the switch write_vcf and --py_hash_order set): the block of the variant is looked up in them
     if pre is not None:
         pre["ready"].wait()
@@ -434,7 +441,7 @@ def _main(argv, state):
                 names = None
                 if args.output_read_ids == 1 or (args.py_hash_order == 1 and os.environ.get("PHZ_PYORDER_PYTHON") == "1"):
                     names = interners[chrom].names          # a list of str: the host row twin and the pure-Python raw-byte twin index it
-                elif args.py_hash_order == 1:
+                elif args.py_hash_order == 1 or args.output_read_haplotypes == 1:
                     names = interners[chrom].pool() if hasattr(interners[chrom], "pool") else interners[chrom].names      # (blob, offsets): what the native raw-byte tier reads
                 items.append((chrom, shards[chrom].to(device), len(interners[chrom]), names))
         eng.add_shards(bi, items)                # all chromosomes of the BAM in one K_map submission
@@ -472,6 +479,12 @@ def _main(argv, state):
         if found == 0:
             say("     variant %s is in no phased block: no network files written" % args.output_network)
         mark("network of " + args.output_network)
+    if args.output_read_haplotypes == 1:
+        # every block's reads at once, from the read lists the tally left in HBM (phaser_amd/readhap.py)
+        rh = eng.read_haplotypes()
+        pdist.write_files([(args.o + ".read_haplotypes.txt", [rh["text"]])], threads=1)
+        say("     %d (block, bam, read) rows written to %s.read_haplotypes.txt" % (len(rh["records"]), args.o))
+        mark("read haplotypes")
     if files is not None:
         for line in eng.log[n_before:]:
             say(line)

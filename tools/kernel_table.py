@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel fingerprint of a HIP translation unit's device side, to show that a host-side change left the kernels alone.
   tools/kernel_table.py dump <source.hip> <out.json>        cross-compile the device side for gfx950 with the build's flags; per kernel symbol:
-                                                            sha256 of its llvm-objdump -d text (addresses / comments stripped) + the resource notes
+                                                            sha256 of its llvm-objdump -d text (addresses / comments / alignment padding stripped) + the resource notes
   tools/kernel_table.py compare <before.json> <after.json> <out.txt>      two-column table, one kernel per entry
 Needs no GPU.  The LLVM tools are taken from $ROCM_PATH/llvm/bin (default /opt/rocm)."""
 import hashlib, json, os, re, subprocess, sys, tempfile
@@ -24,7 +24,7 @@ def dump(src, out):
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             cur = m.group(1); code[cur] = []
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":          # ("...": the zero padding up to the next symbol's alignment, not part of the kernel)
             code[cur].append(re.sub(r"\s*//.*$", "", line).strip())
     tab = {}
     for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
@@ -39,7 +39,7 @@ def compare(before, after, out):
     b, a = json.load(open(before)), json.load(open(after))
     fmt = lambda r: "-" if r is None else "%s v%s a%s s%s spill %s/%s lds %s scratch %s" % ((r["sha"],) + tuple(r[k] for k in KEYS))
     lines = ["per kernel symbol, device side cross-compiled for gfx950 with the build's flags (-O3 -std=c++17 -fPIC --cuda-device-only --no-gpu-bundle-output):",
-             "sha256[:16] of the llvm-objdump -d text (addresses and comments stripped), then VGPRs, AGPRs, SGPRs, spills vgpr/sgpr, LDS bytes, scratch bytes from llvm-readelf --notes",
+             "sha256[:16] of the llvm-objdump -d text (addresses, comments and alignment padding stripped), then VGPRs, AGPRs, SGPRs, spills vgpr/sgpr, LDS bytes, scratch bytes from llvm-readelf --notes",
              "", "%-8s %s" % ("status", "symbol"), "         before | after", ""]
     changed = 0
     for k in sorted(set(a) | set(b)):
