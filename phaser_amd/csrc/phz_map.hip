@@ -26,6 +26,9 @@
 // k_chunk_scan / k_chunk_base prefix-sum the per-tile totals; k_compact copies every slot to its final
 // offset, so the call list is in mapper order with no inter-workgroup dependency inside k_map (a
 // decoupled look-back was measured 0.8 ms slower here: tiles finish faster than descriptors travel).
+// A step is five launches (k_tile_window, k_map, k_chunk_scan, k_chunk_base, k_compact) and one host wait.  k_chunk_base also computes the per-shard
+// totals and stores the words the host reads -- calls of the batch, densest tile, calls per shard, overflow cursor -- straight into their page-locked
+// host image: no copy follows the last kernel.  (A submission of more than a million tiles has a sixth launch, k_shard_totals, for those.)
 #include "phz_internal.h"
 #include "phz_lbound.h"
 #include <stdlib.h>
@@ -433,7 +436,8 @@ __global__ void k_tile_window(MapBatch bt, int tile_reads) {
     const int64_t last = (t + 1) * tile_reads - 1 < n ? (t + 1) * tile_reads - 1 : n - 1;
     const long long key2 = (long long)pos[last] + MAP_COVER;
     // both lower bounds in ONE loop over the whole table: their probes are independent, so the two chains of dependent loads
-    // overlap instead of following each other
+    // overlap instead of following each other.  (Round 15: a 9-way search, 8 independent probes per bound and round, 6 rounds instead of 17 -- the pre-pass
+    // took 37.5 us against 35.0: its time is the four scattered lines every thread fetches (pos and cigar_off at both ends of its tile), not this chain.)
     int lo = 0, hi = nv, lo2 = 0, hi2 = nv;
     while (lo < hi || lo2 < hi2) {
         const int m = (lo + hi) >> 1, m2 = (lo2 + hi2) >> 1;
@@ -896,11 +900,42 @@ __global__ __launch_bounds__(1024) void k_chunk_scan(const int32_t *tile_total, 
     }
 }
 
+// calls before global tile T over all shards (T < ntiles)
+__device__ __forceinline__ int64_t calls_before(const int64_t *chunk_base, const int32_t *tile_pref, int64_t T) {
+    return chunk_base[T >> 10] + tile_pref[T];
+}
+
+// What the host reads when the stream has drained, and where it goes: `host` is the page-locked image of the MapScalars words (hipHostMalloc memory is mapped
+// into the device's address space, so the kernel stores straight into it -- as PhzMail's gather kernel does -- and no copy follows the last kernel of a step).
+struct TotalsOut {
+    const int64_t *tile0; int n_shards; int64_t ntiles;
+    const int32_t *tile_pref;
+    int64_t *shard_base;                      // [n_shards], device: first call of the shard in the batch-wide numbering (k_compact)
+    const unsigned long long *cursor;         // the overflow area's cursor: final once k_map has completed, i.e. for every kernel behind it on the stream
+    unsigned long long *host;                 // [0] calls of the batch, [1] densest tile, [2 + s] calls of shard s, [2 + n_shards] the cursor
+};
+// per shard: offset of its first call in the batch-wide numbering and its number of calls (chunk_base: the LDS copy or the array in global memory)
+__device__ __forceinline__ void shard_total(const TotalsOut &o, int s, const int64_t *chunk_base, int64_t total) {
+    const int64_t a = o.tile0[s], b = o.tile0[s + 1];
+    const int64_t lo = a < o.ntiles ? calls_before(chunk_base, o.tile_pref, a) : total;
+    const int64_t hi = b < o.ntiles ? calls_before(chunk_base, o.tile_pref, b) : total;
+    o.shard_base[s] = lo;
+    o.host[2 + s] = (unsigned long long)(hi - lo);
+}
+__device__ __forceinline__ void batch_words(const TotalsOut &o, unsigned long long total, unsigned long long max_tile) {
+    o.host[0] = total; o.host[1] = max_tile; o.host[2 + o.n_shards] = *o.cursor;
+}
+
+// One workgroup: the exclusive scan of the chunk sums and the densest tile -> scal[0] total, scal[1] max tile.  While the chunk bases fit its LDS copy
+// (BASE_LDS chunks = a million tiles; `merged`) it also does k_shard_totals' work after its last barrier, from that copy: one launch fewer per step, and
+// no reading back of global memory it has just written.
+constexpr int BASE_LDS = 1024;
 __global__ __launch_bounds__(1024) void k_chunk_base(const int64_t *chunk_sum, const int32_t *chunk_max, int nchunks, int64_t *chunk_base,
-                                                     unsigned long long *scal /* [0] total, [1] max tile */) {
+                                                     unsigned long long *scal, bool merged, TotalsOut o) {
     __shared__ long long s_w[16];
     __shared__ long long s_carry;
     __shared__ int s_m[16];
+    __shared__ int64_t s_base[BASE_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_carry = 0;
     int mx = 0;
@@ -919,7 +954,7 @@ __global__ __launch_bounds__(1024) void k_chunk_base(const int64_t *chunk_sum, c
         __syncthreads();
         long long before = s_carry;
         for (int w2 = 0; w2 < wave; w2++) before += s_w[w2];
-        if (i < nchunks) chunk_base[i] = before + x - v;
+        if (i < nchunks) { chunk_base[i] = before + x - v; if (merged) s_base[i] = before + x - v; }      // (merged: nchunks <= BASE_LDS)
         __syncthreads();
         if (tid == 1023) s_carry = before + x;
         __syncthreads();
@@ -928,12 +963,23 @@ __global__ __launch_bounds__(1024) void k_chunk_base(const int64_t *chunk_sum, c
     for (int d = 32; d >= 1; d >>= 1) { int y = __shfl_xor(mx, d); mx = y > mx ? y : mx; }
     if (lane == 0) s_m[wave] = mx;
     __syncthreads();
+    const long long total = s_carry;
     if (tid == 0) {
         int m = 0;
         for (int w2 = 0; w2 < 16; w2++) m = s_m[w2] > m ? s_m[w2] : m;
-        scal[0] = (unsigned long long)s_carry;
+        scal[0] = (unsigned long long)total;
         scal[1] = (unsigned long long)m;
+        if (merged) batch_words(o, (unsigned long long)total, (unsigned long long)m);
     }
+    if (merged)
+        for (int s = tid; s < o.n_shards; s += 1024) shard_total(o, s, s_base, total);
+}
+
+// the per-shard totals of a submission of more than BASE_LDS chunks, from the chunk bases in global memory
+__global__ void k_shard_totals(const int64_t *chunk_base, const unsigned long long *scal, TotalsOut o) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s == 0) batch_words(o, scal[0], scal[1]);
+    if (s < o.n_shards) shard_total(o, s, chunk_base, (int64_t)scal[0]);
 }
 
 struct CompactArgs {
@@ -945,23 +991,6 @@ struct CompactArgs {
     const uint32_t *tile_ovf;             // first slot of a tile with more than slot_cap calls (overflow area), 0xFFFFFFFF: it did not fit
 };
 
-// calls before global tile T over all shards (T < ntiles)
-__device__ __forceinline__ int64_t calls_before(const int64_t *chunk_base, const int32_t *tile_pref, int64_t T) {
-    return chunk_base[T >> 10] + tile_pref[T];
-}
-
-// per shard: offset of its first call in the batch-wide numbering and its number of calls -> scal[2 + s] (scal[0] total, [1] max tile)
-__global__ void k_shard_totals(const int64_t *tile0, int n_shards, int64_t ntiles, const int32_t *tile_pref, const int64_t *chunk_base,
-                               unsigned long long *scal, int64_t *shard_base) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n_shards) return;
-    const int64_t a = tile0[s], b = tile0[s + 1];
-    const int64_t lo = a < ntiles ? calls_before(chunk_base, tile_pref, a) : (int64_t)scal[0];
-    const int64_t hi = b < ntiles ? calls_before(chunk_base, tile_pref, b) : (int64_t)scal[0];
-    shard_base[s] = lo;
-    scal[2 + s] = (unsigned long long)(hi - lo);
-}
-
 // One wave per CT consecutive tiles.  A lane first fetches one tile's bookkeeping (count, shard, destination, first record), so the
 // chain of dependent loads a tile needs is paid once per CT tiles; the wave then walks the CT slots as ONE flat list of calls, UNR
 // elements per lane in flight, each finding its tile by a lower bound over the wave's prefix in LDS.  One wave per tile was bound
@@ -972,9 +1001,19 @@ __global__ void k_shard_totals(const int64_t *tile0, int n_shards, int64_t ntile
 #define PHZ_CT 4
 #endif
 constexpr int CT = PHZ_CT, CT_UNR = 4;
-template <bool UNI>
+// where a shard's calls go (the output part of its ShardDev record)
+struct ShardOut { int32_t *o_read, *o_var; uint8_t *o_code; uint32_t *o_aux0, *o_aux1; int64_t cap; };
+__device__ __forceinline__ ShardOut shard_out(const ShardDev &sh) { return ShardOut{sh.o_read, sh.o_var, sh.o_code, sh.o_aux0, sh.o_aux1, sh.cap}; }
+
+// UNI: all CT tiles of the wave belong to one shard (all but 21 waves of a genome), whose output pointers `out0` were loaded once, right after the shard was
+// known -- inside the loop they are loaded again in every round, behind the staging loads, because the stores between them may alias the record
+// (114 -> 81 us per genome step).
+// AUX: some shard of the submission has the two text planes (decided by the host; without them the branch and its side-plane loads are not compiled in:
+// 114 -> 105 us alone, 81 -> 70 us on top of the hoisted loads).  (The workgroup barrier below as a wave-local ordering point -- the four waves share
+// nothing -- was worth 0.3 us: left as it was.)
+template <bool UNI, bool AUX>
 __device__ __forceinline__ void compact_run(const CompactArgs &c, const int *pref, const int64_t *dstv, const int32_t *r0v, const int32_t *siv, const int64_t *slotv,
-                                            int64_t T0, int M, int lane, int si0) {
+                                            int M, int lane, const ShardOut &out0) {
     for (int e0 = lane; e0 < M; e0 += 64 * CT_UNR) {
         int k_[CT_UNR]; uint2 w_[CT_UNR]; int64_t g_[CT_UNR];
 #pragma unroll
@@ -993,13 +1032,13 @@ __device__ __forceinline__ void compact_run(const CompactArgs &c, const int *pre
             if (e >= M) break;
             const int k = k_[u];
             const uint2 w = w_[u];
-            const ShardDev &sh = c.shards[UNI ? si0 : siv[k]];
+            const ShardOut sh = UNI ? out0 : shard_out(c.shards[siv[k]]);
             const int64_t o = dstv[k] + (e - pref[k]);
             if (o < sh.cap) {
                 sh.o_read[o] = r0v[k] + (int32_t)(w.y & 0x3FFu);
                 sh.o_var[o] = (int32_t)w.x;
                 sh.o_code[o] = (uint8_t)((w.y >> 10) & 15u);
-                if (sh.o_aux0) {             // the two planes only the mapper's text output reads (NULL for a caller that wants (record, variant, code))
+                if (AUX && sh.o_aux0) {      // the two planes only the mapper's text output reads (NULL for a caller that wants (record, variant, code))
                     uint32_t a0 = w.y >> 16, a1 = 0u;
                     if (w.y & 0x8000u) a0 = c.side[g_[u]];
                     if (w.y & 0x4000u) a1 = c.side[c.slots + g_[u]];
@@ -1011,6 +1050,7 @@ __device__ __forceinline__ void compact_run(const CompactArgs &c, const int *pre
     }
 }
 
+template <bool AUX>
 __global__ __launch_bounds__(256) void k_compact(CompactArgs c) {
     __shared__ int s_pref[4][CT + 1];
     __shared__ int64_t s_dst[4][CT], s_slot[4][CT];
@@ -1038,17 +1078,17 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs c) {
     __syncthreads();
     const int M = __builtin_amdgcn_readlane(incl, CT - 1);
     if (M == 0) return;
-    const int si0 = __builtin_amdgcn_readfirstlane(si);
+    const int si0 = __builtin_amdgcn_readfirstlane(si);      // (lane 0 holds tile T0 < ntiles whenever M > 0)
     const bool uni = __ballot(si >= 0 && si != si0) == 0ull;
-    if (uni) compact_run<true>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], T0, M, lane, si0);
-    else compact_run<false>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], T0, M, lane, si0);
+    if (uni) compact_run<true, AUX>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, shard_out(c.shards[si0]));
+    else compact_run<false, AUX>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, ShardOut{});
 }
 
 // ---- layouts of the buffers the driver carves into parts: byte offsets computed once, typed pointers handed out for a device buffer or its pinned image
 template <class T> static T *part_at(const DevBuf &b, size_t off) { return (T *)((char *)b.p + off); }
 
 // ctx->map.tab and its image ctx->map.tab_host: [ShardDev x m][tile0 x (m+1)][shard_base x m][OvfArea].  [0, table_bytes) is the shard table a repeated
-// submission does not upload again; shard_base exists on the device only (k_shard_totals recomputes it in every attempt)
+// submission does not upload again; shard_base exists on the device only (the totals kernel recomputes it in every attempt)
 struct MapTab {
     size_t off_tile0, off_base, off_ovf;
     explicit MapTab(int m) : off_tile0((size_t)m * sizeof(ShardDev)), off_base(off_tile0 + (size_t)(m + 1) * 8), off_ovf(off_base + (size_t)m * 8) {}
@@ -1069,11 +1109,15 @@ struct MapDesc {
     int64_t *chunk_base(const DevBuf &b) const { return part_at<int64_t>(b, off_base); }
     int32_t *chunk_max(const DevBuf &b) const { return part_at<int32_t>(b, off_max); }
 };
-// ctx->scalars and its pinned mirror ctx->h_scalars, 8-byte words: [0] calls of the batch, [1] densest tile, [2, 2 + m) calls per shard, [2 + m] overflow-area cursor
+// ctx->scalars, the device block, 8-byte words: [0] calls of the batch, [1] densest tile, [2] the overflow-area cursor k_map steps.
+// ctx->h_scalars, its page-locked image, written by the totals kernel (TotalsOut) and read by the host: [0] calls of the batch, [1] densest tile,
+// [2, 2 + m) calls per shard -- these exist in the image only --, [2 + m] the cursor
 struct MapScalars {
     int m;
-    size_t readback_bytes() const { return (size_t)8 * (m + 3); }
-    size_t bytes() const { return readback_bytes() + 128; }
+    size_t dev_bytes() const { return (size_t)8 * 3 + 128; }
+    size_t host_bytes() const { return (size_t)8 * (m + 3) + 128; }
+    unsigned long long *dev_words(const DevBuf &b) const { return part_at<unsigned long long>(b, 0); }
+    unsigned long long *dev_cursor(const DevBuf &b) const { return dev_words(b) + 2; }
     unsigned long long *words(const DevBuf &b) const { return part_at<unsigned long long>(b, 0); }
     unsigned long long &shard_calls(const DevBuf &b, int k) const { return words(b)[2 + k]; }
     unsigned long long *cursor(const DevBuf &b) const { return words(b) + 2 + m; }
@@ -1081,10 +1125,12 @@ struct MapScalars {
 
 // the PHZ_MAP_* switches of one submission (read per call: tests change them between calls on one ctx)
 struct MapKnobs {
-    int blk, rpt, dbg; unsigned dyn_lds; bool two_planes;
+    int blk, rpt, dbg, merge_chunks; unsigned dyn_lds; bool two_planes;
     static int positive(const char *name, int dflt) { const char *e = getenv(name); return e && atoi(e) > 0 ? atoi(e) : dflt; }
     // (PHZ_MAP_DYNLDS, an experiment: bytes of dynamic LDS nobody uses, to bound the workgroups per CU)
-    MapKnobs() : blk(positive("PHZ_MAP_BLOCK", 128)), rpt(positive("PHZ_MAP_RPT", 2)), dyn_lds((unsigned)positive("PHZ_MAP_DYNLDS", 0)), two_planes(getenv("PHZ_MAP_TWO_PLANES") != nullptr) {
+    // PHZ_MAP_MERGE_CHUNKS: the largest chunk count whose per-shard totals k_chunk_base computes itself (tests: 1, so that a submission of two chunks takes the
+    // separate k_shard_totals launch of a submission beyond a million tiles)
+    MapKnobs() : blk(positive("PHZ_MAP_BLOCK", 128)), rpt(positive("PHZ_MAP_RPT", 2)), merge_chunks(positive("PHZ_MAP_MERGE_CHUNKS", BASE_LDS)), dyn_lds((unsigned)positive("PHZ_MAP_DYNLDS", 0)), two_planes(getenv("PHZ_MAP_TWO_PLANES") != nullptr) {
         const char *e = getenv("PHZ_MAP_DBG"); dbg = e ? atoi(e) : 0;
     }
 };
@@ -1095,7 +1141,7 @@ struct MapSubmission {
     const int n; const phz_reads *r; const phz_variants *v; const int baseq; const phz_calls *out; int64_t *n_calls;
     const MapKnobs knobs; int tile_reads = 0;
     std::vector<int> live; std::vector<int64_t> tile0;          // live shards (records and variants present); first tile of each, then the tile count
-    int m = 0, nchunks = 0; int64_t ntiles = 0; bool one_plane = false;
+    int m = 0, nchunks = 0; int64_t ntiles = 0; bool one_plane = false, text_planes = false;
     MapTab tab{0}; MapDesc desc{0, 0}; MapScalars scal{0};
     float ms_total = 0;
 
@@ -1140,6 +1186,7 @@ struct MapSubmission {
             if (!d.o_aux0 || !d.o_aux1) { d.o_aux0 = nullptr; d.o_aux1 = nullptr; }           // both or none
             d.cap = out[i].cap;
             if (!d.bq) one_plane = false;
+            if (d.o_aux0) text_planes = true;           // some shard wants the two text planes: k_compact's instantiation that writes them
         }
         memcpy(tab.tile0(M.tab_host), tile0.data(), (size_t)(m + 1) * 8);
         const char *img = (const char *)hs;
@@ -1158,8 +1205,8 @@ struct MapSubmission {
     // deep sample with one dense region).  PHZ_MAP_SLOT_CAP: another slot size (tests: 8, so that most tiles overflow).
     int reserve() {
         auto &M = ctx->map;
-        if (int s = reserve_all(ctx, {{M.tile_w0, (size_t)ntiles * 16}, {S[SC_MAP_TILE_TOTAL], (size_t)ntiles * 4}, {M.desc, desc.bytes}, {ctx->scalars, scal.bytes()}})) return s;
-        if (int s = phz_reserve_host(ctx, ctx->h_scalars, scal.bytes())) return s;
+        if (int s = reserve_all(ctx, {{M.tile_w0, (size_t)ntiles * 16}, {S[SC_MAP_TILE_TOTAL], (size_t)ntiles * 4}, {M.desc, desc.bytes}, {ctx->scalars, scal.dev_bytes()}})) return s;
+        if (int s = phz_reserve_host(ctx, ctx->h_scalars, scal.host_bytes())) return s;
         if (int s = phz_reserve(ctx, S[SC_MAP_TILE_OVF], (size_t)ntiles * 4)) return s;
         if (M.slot_cap <= 0 || M.tile_reads != tile_reads) {
             M.slot_cap = tile_reads / 2 < 64 ? 64 : tile_reads / 2; M.tile_reads = tile_reads;
@@ -1180,7 +1227,7 @@ struct MapSubmission {
         bt.stage = scr<uint2>(SC_MAP_STAGE); bt.side = (uint32_t *)(bt.stage + slots); bt.slots = (int64_t)slots;          // [packed record x slots][side word x 2 slots]
         bt.slot_cap = M.slot_cap;
         OvfArea *h_ov = tab.ovf(M.tab_host), *d_ov = tab.ovf(M.tab);
-        h_ov->tile_first = scr<uint32_t>(SC_MAP_TILE_OVF); h_ov->cursor = scal.cursor(ctx->scalars); h_ov->base = (long long)base_slots; h_ov->cap = (long long)M.ovf_cap;
+        h_ov->tile_first = scr<uint32_t>(SC_MAP_TILE_OVF); h_ov->cursor = scal.dev_cursor(ctx->scalars); h_ov->base = (long long)base_slots; h_ov->cap = (long long)M.ovf_cap;
         const long long img[5] = {(long long)(intptr_t)h_ov->tile_first, (long long)(intptr_t)h_ov->cursor, h_ov->base, h_ov->cap, (long long)(intptr_t)d_ov};
         if (memcmp(img, M.ovf_image, sizeof img) != 0) {
             PHZ_HIP(ctx, hipMemcpyAsync(d_ov, h_ov, sizeof(OvfArea), hipMemcpyHostToDevice, sm));
@@ -1195,7 +1242,7 @@ struct MapSubmission {
         else if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true>), grid, block, knobs.dyn_lds, sm, bt);
         else hipLaunchKernelGGL((k_map<B, R, false>), grid, block, knobs.dyn_lds, sm, bt);
     }
-    // ---- one attempt: pre-pass, k_map between its two events, the scan of the tile totals, per-shard totals, compaction, the words read back.  WAIT
+    // ---- one attempt: pre-pass, k_map between its two events, the scan of the tile totals, chunk bases + per-shard totals + the host's words, compaction.  WAIT
     int attempt() {
         auto &M = ctx->map;
         MapBatch bt;
@@ -1209,20 +1256,25 @@ struct MapSubmission {
         if (knobs.blk == 128) launch_k_map<128, 2>(bt); else launch_k_map<256, 2>(bt);
         PHZ_HIP(ctx, hipEventRecord(M.ev[1], sm));
         int32_t *tile_pref = desc.tile_pref(M.desc); int64_t *chunk_sum = desc.chunk_sum(M.desc), *chunk_base = desc.chunk_base(M.desc); int32_t *chunk_max = desc.chunk_max(M.desc);
-        unsigned long long *d_words = scal.words(ctx->scalars);
+        unsigned long long *d_words = scal.dev_words(ctx->scalars);
         hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)nchunks), dim3(1024), 0, sm, (const int32_t *)bt.tile_total, ntiles, tile_pref, chunk_sum, chunk_max);
-        hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(1024), 0, sm, (const int64_t *)chunk_sum, (const int32_t *)chunk_max, nchunks, chunk_base, d_words);
-        hipLaunchKernelGGL(k_shard_totals, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, sm, bt.tile0, m, ntiles, (const int32_t *)tile_pref, (const int64_t *)chunk_base, d_words,
-                           tab.shard_base(M.tab));
+        // the words the host reads after the wait are stored into their page-locked image by the totals kernel: no copy ends the step
+        TotalsOut to;
+        to.tile0 = bt.tile0; to.n_shards = m; to.ntiles = ntiles; to.tile_pref = tile_pref; to.shard_base = tab.shard_base(M.tab);
+        to.cursor = scal.dev_cursor(ctx->scalars); to.host = scal.words(ctx->h_scalars);
+        const bool merged = nchunks <= BASE_LDS && nchunks <= knobs.merge_chunks;
+        hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(1024), 0, sm, (const int64_t *)chunk_sum, (const int32_t *)chunk_max, nchunks, chunk_base, d_words, merged, to);
+        if (!merged) hipLaunchKernelGGL(k_shard_totals, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, sm, (const int64_t *)chunk_base, (const unsigned long long *)d_words, to);
         CompactArgs c;
         c.stage = bt.stage; c.side = bt.side; c.slots = bt.slots;
         c.shards = bt.shards; c.tile0 = bt.tile0; c.n_shards = m;
         c.tile_total = bt.tile_total; c.tile_pref = tile_pref; c.chunk_base = chunk_base; c.shard_base = tab.shard_base(M.tab);
         c.tile_w0 = bt.tile_w0;
         c.slot_cap = bt.slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = scr<const uint32_t>(SC_MAP_TILE_OVF);
-        hipLaunchKernelGGL(k_compact, dim3((unsigned)((ntiles + 4 * CT - 1) / (4 * CT))), dim3(256), 0, sm, c);
+        const dim3 cgrid((unsigned)((ntiles + 4 * CT - 1) / (4 * CT)));
+        if (text_planes) hipLaunchKernelGGL(k_compact<true>, cgrid, dim3(256), 0, sm, c);
+        else hipLaunchKernelGGL(k_compact<false>, cgrid, dim3(256), 0, sm, c);
         PHZ_HIP(ctx, hipGetLastError());
-        PHZ_HIP(ctx, hipMemcpyAsync(scal.words(ctx->h_scalars), d_words, scal.readback_bytes(), hipMemcpyDeviceToHost, sm));
         PHZ_HIP(ctx, hipStreamSynchronize(sm));
         float ms = 0;
         PHZ_HIP(ctx, hipEventElapsedTime(&ms, M.ev[0], M.ev[1]));
@@ -1260,7 +1312,7 @@ struct MapSubmission {
 }  // namespace
 
 // All shards of a submission run through ONE grid per stage (pre-pass, k_map, tile scan, per-shard totals, compaction): a whole
-// genome is 5 launches and one host wait, with no per-shard ramp-up / tail.
+// genome is 5 launches and one host wait (no read-back copy: the totals kernel stores the host's words itself), with no per-shard ramp-up / tail.
 // (Tried and dropped, round 3: k_map writing every call to its final place, the calls before a tile found by decoupled look-back over
 // per-tile status words -- no staging, no k_compact.  A tile knows its count only at the END of its work (the count needs the quality
 // bytes), so its flush waits for every earlier tile still in flight: 3.01 ms against 1.32 + 0.16 ms for k_map + k_compact.)  A batch whose densest tiles overflow
