@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_COUNT = 10 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_COUNT = 12 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -792,6 +792,39 @@ int phz_annot_pairs(phz_ctx *ctx, const phz_annot_in *in, int64_t batch_rows, ph
  * head[a] \t side[a] \t side[b] \t cis|trans \t read_backed \n.  PHZ_E_ARG when a record names an entry or a slot out of range.  out is malloc'd (phz_buf_free). */
 int phz_annot_rows(const phz_annot_rec *rec, int64_t n_rows, int64_t n_entries, const int32_t *slot_of, int64_t n_slots, const char *head,
                    const int64_t *head_off, const char *side, const int64_t *side_off, int32_t threads, char **out, int64_t *out_len);
+
+/* ---- phaser_ae_test (phaser_amd/ae_test.py; no counterpart in the reference): allelic-imbalance test of aCount|bCount cells --------------------
+ * K_binom: the exact two-sided binomial test of scipy.stats.binomtest(k, n, p0, alternative="two-sided") for n_tests cells, k = a[t], n = a[t] + b[t],
+ * pmf(i) = C(n, i) p0^i (1 - p0)^(n - i), all in fp64:
+ *   n < max(min_cov, 1), or a or b negative     the cell is not tested: pvalue[t] = NaN
+ *   k == p0 * n (the product taken in double)   1
+ *   k <  p0 * n    j = the smallest i in [ceil(p0 n), n] with pmf(i) <= pmf(k) (1 + 1e-7);  P = sum_{i <= k} pmf(i) + sum_{i >= j} pmf(i) (no such i: no second sum)
+ *   otherwise      j = the largest i in [0, floor(p0 n)] with pmf(i) <= pmf(k) (1 + 1e-7);  P = sum_{i >= k} pmf(i) + sum_{i <= j} pmf(i)
+ *   pvalue[t] = min(1, P)
+ * The pmf at a start index is exp(lgamma(n+1) - lgamma(i+1) - lgamma(n-i+1) + i log(p0) + (n-i) log1p(-p0)); a tail is summed outward from its start index by
+ * the pmf recurrence until a term falls below 1e-18 of the running sum.  p0 must lie strictly between 0 and 1 (else PHZ_E_ARG); a[t] + b[t] must fit in
+ * int32: checked for PHZ_HOST inputs (PHZ_E_ARG), the caller's guarantee with PHZ_DEVICE.  The kernel is timed into PHZ_T_BINOM. */
+int phz_binom_test(phz_ctx *ctx, int64_t n_tests, const int32_t *a, const int32_t *b, double p0, int32_t min_cov, double *pvalue, int space);
+
+/* K_bh: Benjamini-Hochberg q-values (scipy.stats.false_discovery_control(p, method="bh")) of every column of the row-major n_rows x n_cols matrix pvalue,
+ * independently; NaN = not tested, every other value lies in [0, 1].  m = the non-NaN cells of the column, n_tested[c] = m; the cell of ascending rank r
+ * (1-based) gets min(1, min over ranks s >= r of p_(s) * (m / s)), the operations in exactly that order; NaN cells stay NaN.  Tied p-values receive the same
+ * q.  At most 2^31 - 1 cells; qvalue must not overlap pvalue.  The kernels (compaction, two sorts, the walk) are timed into PHZ_T_BH. */
+int phz_bh_adjust(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const double *pvalue, double *qvalue, int64_t *n_tested, int space);
+
+/* The text of an expression matrix as phaser_expr_matrix writes it -- a header line "#contig start stop name <samples...>", then one row per gene: four
+ * leading columns and one aCount|bCount cell per sample, tab-separated -- parsed with host threads.  Lines end in \n or \r\n; empty lines are skipped.
+ * Two calls: with a == NULL the text is only measured (*n_rows, *n_cols = sample columns of the header, *header_len = bytes of the first line without its
+ * line end); with the arrays given they are filled: a, b row-major [n_rows * n_cols], and per row the byte range text[lead_off[r], lead_off[r] + lead_len[r])
+ * of its four leading columns (the whole line when it has fewer).  A cell that is not <digits>|<digits>, whose counts do not add up inside int32, or that the
+ * row does not have gives a = b = -1 (phz_binom_test leaves it untested); cells beyond the header's columns are ignored.  PHZ_E_ARG when the text has no header. */
+int phz_aematrix_parse(const char *text, int64_t len, int32_t threads, int64_t *n_rows, int64_t *n_cols, int64_t *header_len, int32_t *a, int32_t *b,
+                       int64_t *lead_off, int32_t *lead_len);
+
+/* Rows of an output matrix of phaser_ae_test, threaded: per row its leading columns (the byte ranges phz_aematrix_parse returned) and one cell per column,
+ * value[r * n_cols + c] printed as printf's %.6g, NaN as NA; tab-separated, every row ends in \n.  out is malloc'd (phz_buf_free). */
+int phz_aetest_rows(const char *text, const int64_t *lead_off, const int32_t *lead_len, int64_t n_rows, int64_t n_cols, const double *value, int32_t threads,
+                    char **out, int64_t *out_len);
 
 /* Output rows of phaser_gene_ae (:147-163), threaded.  Keys are bam * n_features + feature.  Pools: items followed by '\n'.
  * out is malloc'd (phz_buf_free). */

@@ -43,6 +43,10 @@ enum PhzScratch {
     // value bytes, survivors per workgroup + scan, (runs, rows) per workgroup + scan, the sort's digit table, the scans' temporary
     SC_RH_FLAG = 0, SC_RH_VBLK = 1, SC_RH_VSIDE = 2, SC_RH_KEY0 = 3, SC_RH_KEY1 = 4, SC_RH_VAL0 = 5, SC_RH_VAL1 = 6, SC_RH_LIVE_COUNT = 7, SC_RH_LIVE_BASE = 8,
     SC_RH_RUN_COUNT = 9, SC_RH_RUN_BASE = 10, SC_RH_SORT_COUNT = 11, SC_RH_SCAN_TMP = 12,
+    // K_bh (phz_bh_adjust): place of every cell among the tested ones, tested cells per column + their scan, the two (p bits, cell) buffers of the sort by p, the
+    // two column-key buffers of the sort by column, the sorts' digit table, the scans' temporary
+    SC_BH_POS = 0, SC_BH_COL_COUNT = 1, SC_BH_COL_OFF = 2, SC_BH_KEY0 = 3, SC_BH_KEY1 = 4, SC_BH_CELL0 = 5, SC_BH_CELL1 = 6, SC_BH_CKEY0 = 7, SC_BH_CKEY1 = 8,
+    SC_BH_SORT_COUNT = 9, SC_BH_SCAN_TMP = 10,
     SC_COUNT = 24
 };
 
