@@ -43,10 +43,11 @@ def batch_phase(ctx, comps, mbs):
     return cs, sub, al, ns
 
 
-@pytest.mark.parametrize("seed,mbs", [(1, 3), (2, 5), (3, 9), (4, 15), (5, 0), (6, 4), (7, 18), (8, 12)])
-def test_device_phase_matches_host_routine(seed, mbs):
-    lib = emu_library()
-    ctx = EmuContext(lib)
+SEED_LISTS = [(1, 3), (2, 5), (3, 9), (4, 15), (5, 0), (6, 4), (7, 18), (8, 12)]
+
+
+def random_list(lib, seed, mbs):
+    """-> (components, what phz_phase_block of `lib` gives for each): 160 random components less the ones the host routine refuses"""
     rng = random.Random(4200 + seed)
     comps = []; want = []
     for t in range(160):
@@ -58,6 +59,11 @@ def test_device_phase_matches_host_routine(seed, mbs):
         if w is None:
             continue
         comps.append((n, edges)); want.append(w)
+    return comps, want
+
+
+def assert_list_matches(ctx, comps, want, mbs):
+    """one phz_phase_components call on `ctx` over the list; every component exactly what the host routine gave.  -> components split or partly unphased"""
     cs, sub, al, ns = batch_phase(ctx, comps, mbs)
     split = 0
     for c, ((n, edges), (wsub, wal, wns)) in enumerate(zip(comps, want)):
@@ -67,4 +73,13 @@ def test_device_phase_matches_host_routine(seed, mbs):
         live = wsub >= 0
         assert np.array_equal(al[lo:hi][live], wal[live]), (n, mbs, edges)
         split += wns != 1 or not live.all()
+    return split
+
+
+@pytest.mark.parametrize("seed,mbs", SEED_LISTS)
+def test_device_phase_matches_host_routine(seed, mbs):
+    lib = emu_library()
+    ctx = EmuContext(lib)
+    comps, want = random_list(lib, seed, mbs)
+    split = assert_list_matches(ctx, comps, want, mbs)
     assert len(comps) > 100 and split > 10

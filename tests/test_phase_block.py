@@ -13,7 +13,8 @@ import pytest
 from conftest import REPO
 
 
-def _oracle_phase(n, edges, mbs):
+def _oracle_inputs(n, edges, mbs):
+    """-> (Phaser, variant names, variant-level neighbours, allele-level neighbours): what phase_block takes"""
     sys.path.insert(0, os.path.join(REPO, "oracle"))
     import phasing_oracle as po
     ph = po.Phaser(["x"], max_block_size=mbs)
@@ -29,6 +30,11 @@ def _oracle_phase(n, edges, mbs):
             ac[a + ":0"].add(b + ":0"); ac[b + ":0"].add(a + ":0"); ac[a + ":1"].add(b + ":1"); ac[b + ":1"].add(a + ":1")
         elif k == 1:
             ac[a + ":0"].add(b + ":1"); ac[b + ":0"].add(a + ":1"); ac[a + ":1"].add(b + ":0"); ac[b + ":1"].add(a + ":0")
+    return ph, names, vc, ac
+
+
+def _oracle_phase(n, edges, mbs):
+    ph, names, vc, ac = _oracle_inputs(n, edges, mbs)
     res = ph.phase_block(names, vc, ac)
     idx = {u: i for i, u in enumerate(names)}
     return [[(idx[x.split(":")[0]], x.split(":")[1]) for x in sub] for sub in res if sub]
