@@ -24,7 +24,7 @@ PHZ_T_BINOM, PHZ_T_BH = 10, 11
 PHZ_T_COUNT = 12
 PHZ_ANNOT_BOTH, PHZ_ANNOT_FIRST = 1, 2
 PHZ_ANNOT_BATCH_ROWS = 1 << 24
-PHZ_C_LINES, PHZ_C_ITEMS, PHZ_C_PAIR_EVENTS, PHZ_C_EDGES, PHZ_C_FAR_LINES, PHZ_C_DIRTY_LISTS, PHZ_C_PAIR_REDOS = 0, 1, 2, 3, 4, 5, 6
+PHZ_C_LINES, PHZ_C_ITEMS, PHZ_C_PAIR_EVENTS, PHZ_C_EDGES, PHZ_C_FAR_LINES, PHZ_C_DIRTY_LISTS, PHZ_C_PAIR_REDOS, PHZ_C_MAP_NARROW = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class PhzError(RuntimeError):

@@ -29,8 +29,16 @@
 // A step is five launches (k_tile_window, k_map, k_chunk_scan, k_chunk_base, k_compact) and one host wait.  k_chunk_base also computes the per-shard
 // totals and stores the words the host reads -- calls of the batch, densest tile, calls per shard, overflow cursor -- straight into their page-locked
 // host image: no copy follows the last kernel.  (A submission of more than a million tiles has a sixth launch, k_shard_totals, for those.)
+// A staged call has one of two forms, chosen by the host for the whole submission (stage_narrow_form, phz_stagepack.h):
+//   * narrow: one 32-bit word, var[0:20) | rec[20:28) | code[28:32) -- when no shard asks for the text planes, a tile has at most 256 records and every
+//     het-SNP table at most 2^20 entries (the headline step; what Engine.add_shards asks for).  k_map<.., NARROW> stores one dword per call, carries neither
+//     the read offsets nor the inserted-text lookup to its flush and has no side planes; k_compact<false, true> loads one dword per call; the staging area is
+//     4 bytes per slot;
+//   * general: the 8-byte record of stage_put plus two side planes (16 bytes per slot) -- everything else, and PHZ_MAP_WIDE_STAGE=1.
+// Slot indices, slot_cap, the overflow area, its cursor and the redo are the same in both.
 #include "phz_internal.h"
 #include "phz_lbound.h"
+#include "phz_stagepack.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -59,7 +67,7 @@ struct MapArgs {
     int nv;
     int baseq;
     // staging slots: global tile t owns stage[t*slot_cap, (t+1)*slot_cap); one packed 8-byte record per call (stage_put):
-    // one store per call here, one load in k_compact
+    // one store per call here, one load in k_compact.  (The narrow instantiations index the same area as 32-bit words: phz_stagepack.h.)
     uint2 *stage;
     uint32_t *side;               // [2*slots] aux words that do not fit the packed record (insertions, offsets >= 2^16)
     int64_t slots;
@@ -243,7 +251,8 @@ __device__ __forceinline__ int masked_base(const MapArgs &a, uint32_t soff, int 
 
 // MODE 0: position rule only, candidates appended to the LDS buffer (no global loads in the divergent walk)
 // MODE 1: count calls, resolving bases in-lane (fallback)      MODE 2: emit calls in-lane (fallback)
-template <int MODE>
+// NARROW (MODE 2 only): the call is staged as the 4-byte word of phz_stagepack.h
+template <int MODE, bool NARROW = false>
 __device__ int walk_read(const MapArgs &a, const VarWin &vw, const CigWin &cw, const CandBuf &cb, int j, int64_t r, int pos,
                          uint32_t c0, uint32_t c1, uint32_t soff, int64_t out_base, int64_t out_limit) {
     int i = vw.lower_bound(vw.w0, pos);
@@ -297,7 +306,8 @@ __device__ int walk_read(const MapArgs &a, const VarWin &vw, const CigWin &cw, c
                             if (MODE == 2) {
                                 const int64_t o = out_base + cnt;
                                 if (o < out_limit) {
-                                    stage_put(a.stage, a.side, a.slots, o, (uint32_t)i, x0, x1, (uint32_t)j, (uint32_t)code);
+                                    if (NARROW) reinterpret_cast<uint32_t *>(a.stage)[o] = stage4_pack((uint32_t)i, (uint32_t)j, (uint32_t)code);
+                                    else stage_put(a.stage, a.side, a.slots, o, (uint32_t)i, x0, x1, (uint32_t)j, (uint32_t)code);
                                 }
                             }
                             cnt++;
@@ -425,19 +435,33 @@ constexpr int MAP_SLACK = 8;       // ... plus this many further entries (probe 
 __global__ void k_tile_window(MapBatch bt, int tile_reads) {
     const int64_t T = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (T == 0) *bt.ovf->cursor = 0ull;                     // the overflow area of this submission's staging starts empty
-    if (T >= bt.ntiles) return;
-    const int si = shard_of(bt.tile0, bt.n_shards, T);
+    const bool live = T < bt.ntiles;
+    const int si = live ? shard_of(bt.tile0, bt.n_shards, T) : 0;
     const ShardDev &sh = bt.shards[si];
-    const int64_t t = T - bt.tile0[si];
+    const int64_t t = live ? T - bt.tile0[si] : 0;
     const int32_t *pos = sh.pos; const uint32_t *cigar_off = sh.cigar_off; const int32_t *vpos = sh.vpos;
     const int nv = sh.nv; const int64_t n = sh.n;
     int32_t *tile_w = bt.tile_w0;
-    const int key = pos[t * tile_reads];
-    const int64_t last = (t + 1) * tile_reads - 1 < n ? (t + 1) * tile_reads - 1 : n - 1;
-    const long long key2 = (long long)pos[last] + MAP_COVER;
+    // Two scattered lines per tile, not four (round 17): a thread loads the FIRST position and the FIRST CIGAR offset of its tile and takes the
+    // two words that end the tile from lane + 1, whose tile starts where this one ends -- cigar_off[last + 1] is the neighbour's first offset, and its first
+    // position is >= pos[last] (records are sorted), so the upper key only grows and the window is a superset of the one pos[last] gave.  The neighbour
+    // serves only when it is the next tile of the SAME shard in the same wave; lane 63 and the last tile of a shard load both words themselves, as does
+    // -- its position only -- a tile whose neighbour starts more than MAP_COVER further on (a gene boundary that falls on a tile boundary: the table
+    // entries inside the jump must not push the tile over MAP_WIN).  Every lane of the wave takes part in the shuffles: the early return is behind them.
+    const int key = live ? pos[t * tile_reads] : 0;
+    const uint32_t coff0 = live ? cigar_off[t * tile_reads] : 0u;
+    const int nb_key = __shfl_down(key, 1);
+    const uint32_t nb_coff0 = (uint32_t)__shfl_down((int)coff0, 1);
+    if (!live) return;
+    const bool more = (t + 1) * tile_reads < n;             // the shard has a next tile: global tile T + 1, which is lane + 1 unless this is lane 63
+    const int64_t last = more ? (t + 1) * tile_reads - 1 : n - 1;
+    const bool nb = more && (threadIdx.x & 63) != 63;
+    const uint32_t coff_end = nb ? nb_coff0 : cigar_off[last + 1];
+    const int pos_end = (nb && (long long)nb_key - key <= MAP_COVER) ? nb_key : pos[last];
+    const long long key2 = (long long)pos_end + MAP_COVER;
     // both lower bounds in ONE loop over the whole table: their probes are independent, so the two chains of dependent loads
     // overlap instead of following each other.  (Round 15: a 9-way search, 8 independent probes per bound and round, 6 rounds instead of 17 -- the pre-pass
-    // took 37.5 us against 35.0: its time is the four scattered lines every thread fetches (pos and cigar_off at both ends of its tile), not this chain.)
+    // took 37.5 us against 35.0: its time was the four scattered lines every thread fetched (pos and cigar_off at both ends of its tile), not this chain.)
     int lo = 0, hi = nv, lo2 = 0, hi2 = nv;
     while (lo < hi || lo2 < hi2) {
         const int m = (lo + hi) >> 1, m2 = (lo2 + hi2) >> 1;
@@ -449,10 +473,10 @@ __global__ void k_tile_window(MapBatch bt, int tile_reads) {
     int len = lo2 - lo + MAP_SLACK;
     int complete = 1 << 30;
     if (len > MAP_WIN) { len = MAP_WIN; complete = 0; }
-    const uint32_t n_ops = cigar_off[last + 1] - cigar_off[t * tile_reads];
+    const uint32_t n_ops = coff_end - coff0;
     tile_w[4 * T] = lo;
     tile_w[4 * T + 1] = len | complete | (si << 16);          // bits 0-15 window length, 16-28 shard of the tile, 30 window complete
-    tile_w[4 * T + 2] = (int32_t)cigar_off[t * tile_reads];            // first CIGAR word of the tile
+    tile_w[4 * T + 2] = (int32_t)coff0;                                // first CIGAR word of the tile
     tile_w[4 * T + 3] = (int32_t)n_ops;
 }
 
@@ -511,7 +535,8 @@ __device__ __forceinline__ int block_scan(const int (&cnt)[RPT], int (&excl)[RPT
 
 // ABL: the ablation switches of PHZ_MAP_DBG are live (profiling build of the same code); the production instantiation sees dbg == 0 at
 // compile time, so none of its tests reach the scalar unit
-template <int MAP_BLOCK, int RPT, bool ABL, bool ONE>
+// NARROW: the 4-byte staging word (phz_stagepack.h); the flush then carries neither the read offsets nor the inserted-text lookup and never touches `side`
+template <int MAP_BLOCK, int RPT, bool ABL, bool ONE, bool NARROW>
 __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile) {
     const int4 tw = *reinterpret_cast<const int4 *>(bt.tile_w0 + 4 * gtile);      // the pre-pass left the tile's shard here: no search
     const int si = (tw.y >> 16) & 0x1FFF;
@@ -716,7 +741,7 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     __syncthreads();
     PHZ_STAMP(4);
     const int ncand = s_ncand;
-    const bool fb = ncand > CAND;              // candidate buffer overflow: complex records fall back to in-lane work
+    const bool fb = ncand > CAND;             // candidate buffer overflow: complex records fall back to in-lane work
     // the bytes of this lane's buffered candidate (if it has one) are requested now and used after the arithmetic below
     uint32_t cq = 0, cs = 0; int cx_off = -1;
     if (!fb && tid < ncand && !(a.dbg & 1)) {
@@ -785,8 +810,12 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
 #pragma unroll
         for (int k = 0; k < RPT; k++) {
             const int j = k * MAP_BLOCK + tid;
+            // (NARROW: the in-lane fallback -- here and in phase 4 -- fetches the record's position and CIGAR range again instead of taking them from rpos_ /
+            // c0_ / c1_.  Those six registers would otherwise stay live to the end of the kernel for this cold path alone, and the two-plane narrow
+            // instantiation then spills a vector register across the walk -- an LDS address, 8 B of scratch -- where the 8-byte form spills none.)
             cnt[k] = fast_[k] ? __popc(vmask_[k])
-                              : (j < nr && walk_on ? walk_read<1>(a, vw, cw, cb, j, r0 + j, rpos_[k], c0_[k], c1_[k], s_soff[j], 0, 0) : 0);
+                              : (j < nr && walk_on ? walk_read<1>(a, vw, cw, cb, j, r0 + j, NARROW ? a.pos[r0 + j] : rpos_[k], NARROW ? s_coff[j] : c0_[k],
+                                                                  NARROW ? s_coff[j + 1] : c1_[k], s_soff[j], 0, 0) : 0);
         }
     }
     PHZ_STAMP(5);
@@ -825,13 +854,15 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
                 if (!((vmask_[k] >> o) & 1)) continue;
                 if (o2 < slot_n) {
                     const int64_t g = slot0 + o2;
-                    stage_put(a.stage, a.side, a.slots, g, (uint32_t)(vw.w0 + base_[k] + o), (uint32_t)(s_vpos[base_[k] + o] - rpos_[k]), 0u,
-                              (uint32_t)j, (codes_[k] >> (4 * o)) & 15u);
+                    if (NARROW) reinterpret_cast<uint32_t *>(a.stage)[g] = stage4_pack((uint32_t)(vw.w0 + base_[k] + o), (uint32_t)j, (codes_[k] >> (4 * o)) & 15u);
+                    else stage_put(a.stage, a.side, a.slots, g, (uint32_t)(vw.w0 + base_[k] + o), (uint32_t)(s_vpos[base_[k] + o] - rpos_[k]), 0u,
+                                   (uint32_t)j, (codes_[k] >> (4 * o)) & 15u);
                 }
                 o2++;
             }
         } else if (fb && cnt[k] > 0) {
-            walk_read<2>(a, vw, cw, cb, j, r0 + j, rpos_[k], c0_[k], c1_[k], s_soff[j], slot0 + off[k], slot0 + slot_n);
+            walk_read<2, NARROW>(a, vw, cw, cb, j, r0 + j, NARROW ? a.pos[r0 + j] : rpos_[k], NARROW ? a.cigar_off[r0 + j] : c0_[k],
+                                 NARROW ? a.cigar_off[r0 + j + 1] : c1_[k], s_soff[j], slot0 + off[k], slot0 + slot_n);
         }
     }
     if (!fb) {
@@ -843,7 +874,8 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
             const int o = (int)s_coff[j] + __popc(s_mask[j] & ((1u << ord) - 1));
             if (o < slot_n) {
                 const int64_t g = slot0 + o;
-                stage_put(a.stage, a.side, a.slots, g, (uint32_t)(vw.w0 + (int)s_var[e]), cand_x0(cb, e), cand_x1(cb, e, key), (uint32_t)j, key & 15u);
+                if (NARROW) reinterpret_cast<uint32_t *>(a.stage)[g] = stage4_pack((uint32_t)(vw.w0 + (int)s_var[e]), (uint32_t)j, key & 15u);
+                else stage_put(a.stage, a.side, a.slots, g, (uint32_t)(vw.w0 + (int)s_var[e]), cand_x0(cb, e), cand_x1(cb, e, key), (uint32_t)j, key & 15u);
             }
         }
     }
@@ -863,12 +895,12 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
 #else
 #define PHZ_MAP_OCC
 #endif
-template <int MAP_BLOCK, int RPT, bool ABL, bool ONE = false>
+template <int MAP_BLOCK, int RPT, bool ABL, bool ONE = false, bool NARROW = false>
 __global__ __launch_bounds__(MAP_BLOCK) PHZ_MAP_OCC void k_map(MapBatch bt) {
     // (XCD-contiguous tile order -- workgroup i runs on XCD i % 8; every XCD given one contiguous eighth of the tiles -- was measured in
     // round 4 for k_map, k_line, k_tile and k_pairs: no gain anywhere, 1.291 against 1.282 ms here.  Neighbouring tiles share only their
     // het-SNP window, which the memory-side cache serves.)
-    map_tile<MAP_BLOCK, RPT, ABL, ONE>(bt, (int64_t)blockIdx.x);
+    map_tile<MAP_BLOCK, RPT, ABL, ONE, NARROW>(bt, (int64_t)blockIdx.x);
 }
 
 // two-level exclusive prefix sum of the per-tile totals: 1024-tile chunks in parallel, then one small pass
@@ -1011,9 +1043,41 @@ __device__ __forceinline__ ShardOut shard_out(const ShardDev &sh) { return Shard
 // AUX: some shard of the submission has the two text planes (decided by the host; without them the branch and its side-plane loads are not compiled in:
 // 114 -> 105 us alone, 81 -> 70 us on top of the hoisted loads).  (The workgroup barrier below as a wave-local ordering point -- the four waves share
 // nothing -- was worth 0.3 us: left as it was.)
-template <bool UNI, bool AUX>
+// NARROW: the slots hold the 4-byte word of phz_stagepack.h (never together with AUX): half the bytes in, no side planes
+template <bool UNI, bool AUX, bool NARROW>
 __device__ __forceinline__ void compact_run(const CompactArgs &c, const int *pref, const int64_t *dstv, const int32_t *r0v, const int32_t *siv, const int64_t *slotv,
                                             int M, int lane, const ShardOut &out0) {
+    static_assert(!(AUX && NARROW), "the narrow staging word carries no text planes");
+    if (NARROW) {
+        const uint32_t *stage4 = reinterpret_cast<const uint32_t *>(c.stage);
+        for (int e0 = lane; e0 < M; e0 += 64 * CT_UNR) {
+            int k_[CT_UNR]; uint32_t w_[CT_UNR];
+#pragma unroll
+            for (int u = 0; u < CT_UNR; u++) {
+                const int e = e0 + 64 * u;
+                int k = 0;
+#pragma unroll
+                for (int st = CT / 2; st > 0; st >>= 1) k += (pref[k + st] <= e) ? st : 0;     // last k with pref[k] <= e
+                k_[u] = k;
+                w_[u] = e < M ? stage4[slotv[k] + (e - pref[k])] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < CT_UNR; u++) {
+                const int e = e0 + 64 * u;
+                if (e >= M) break;
+                const int k = k_[u];
+                const uint32_t w = w_[u];
+                const ShardOut sh = UNI ? out0 : shard_out(c.shards[siv[k]]);
+                const int64_t o = dstv[k] + (e - pref[k]);
+                if (o < sh.cap) {
+                    sh.o_read[o] = r0v[k] + (int32_t)stage4_rec(w);
+                    sh.o_var[o] = (int32_t)stage4_var(w);
+                    sh.o_code[o] = (uint8_t)stage4_code(w);
+                }
+            }
+        }
+        return;
+    }
     for (int e0 = lane; e0 < M; e0 += 64 * CT_UNR) {
         int k_[CT_UNR]; uint2 w_[CT_UNR]; int64_t g_[CT_UNR];
 #pragma unroll
@@ -1050,7 +1114,7 @@ __device__ __forceinline__ void compact_run(const CompactArgs &c, const int *pre
     }
 }
 
-template <bool AUX>
+template <bool AUX, bool NARROW = false>
 __global__ __launch_bounds__(256) void k_compact(CompactArgs c) {
     __shared__ int s_pref[4][CT + 1];
     __shared__ int64_t s_dst[4][CT], s_slot[4][CT];
@@ -1080,8 +1144,8 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs c) {
     if (M == 0) return;
     const int si0 = __builtin_amdgcn_readfirstlane(si);      // (lane 0 holds tile T0 < ntiles whenever M > 0)
     const bool uni = __ballot(si >= 0 && si != si0) == 0ull;
-    if (uni) compact_run<true, AUX>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, shard_out(c.shards[si0]));
-    else compact_run<false, AUX>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, ShardOut{});
+    if (uni) compact_run<true, AUX, NARROW>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, shard_out(c.shards[si0]));
+    else compact_run<false, AUX, NARROW>(c, s_pref[w], s_dst[w], s_r0[w], s_si[w], s_slot[w], M, lane, ShardOut{});
 }
 
 // ---- layouts of the buffers the driver carves into parts: byte offsets computed once, typed pointers handed out for a device buffer or its pinned image
@@ -1126,6 +1190,7 @@ struct MapScalars {
 // the PHZ_MAP_* switches of one submission (read per call: tests change them between calls on one ctx)
 struct MapKnobs {
     int blk, rpt, dbg, merge_chunks; unsigned dyn_lds; bool two_planes;
+    bool wide_stage = positive("PHZ_MAP_WIDE_STAGE", 0) != 0;      // PHZ_MAP_WIDE_STAGE=1: the 8-byte staging record even where the 4-byte word would do (tests, A/B)
     static int positive(const char *name, int dflt) { const char *e = getenv(name); return e && atoi(e) > 0 ? atoi(e) : dflt; }
     // (PHZ_MAP_DYNLDS, an experiment: bytes of dynamic LDS nobody uses, to bound the workgroups per CU)
     // PHZ_MAP_MERGE_CHUNKS: the largest chunk count whose per-shard totals k_chunk_base computes itself (tests: 1, so that a submission of two chunks takes the
@@ -1141,7 +1206,7 @@ struct MapSubmission {
     const int n; const phz_reads *r; const phz_variants *v; const int baseq; const phz_calls *out; int64_t *n_calls;
     const MapKnobs knobs; int tile_reads = 0;
     std::vector<int> live; std::vector<int64_t> tile0;          // live shards (records and variants present); first tile of each, then the tile count
-    int m = 0, nchunks = 0; int64_t ntiles = 0; bool one_plane = false, text_planes = false;
+    int m = 0, nchunks = 0; int64_t ntiles = 0, max_nv = 0; bool one_plane = false, text_planes = false, narrow = false;
     MapTab tab{0}; MapDesc desc{0, 0}; MapScalars scal{0};
     float ms_total = 0;
 
@@ -1187,7 +1252,10 @@ struct MapSubmission {
             d.cap = out[i].cap;
             if (!d.bq) one_plane = false;
             if (d.o_aux0) text_planes = true;           // some shard wants the two text planes: k_compact's instantiation that writes them
+            if (d.nv > max_nv) max_nv = d.nv;
         }
+        // the staging form of the submission (phz_stagepack.h); the profiling instantiation of k_map exists in the general form only
+        narrow = stage_narrow_form(text_planes, tile_reads, max_nv, knobs.wide_stage || knobs.dbg != 0);
         memcpy(tab.tile0(M.tab_host), tile0.data(), (size_t)(m + 1) * 8);
         const char *img = (const char *)hs;
         if (M.tab_image.size() != tab.table_bytes() || M.tab_dev != M.tab.p || memcmp(M.tab_image.data(), img, tab.table_bytes()) != 0) {
@@ -1223,8 +1291,9 @@ struct MapSubmission {
         if (M.ovf_cap < 65536) M.ovf_cap = 65536;
         const size_t slots = base_slots + (size_t)M.ovf_cap;
         if (slots >= 0xFFFFFFF0ull) return phz_fail(ctx, PHZ_E_ARG, "K_map staging area beyond 2^32 slots: submit the shards in smaller batches");
-        if (int s = phz_reserve(ctx, S[SC_MAP_STAGE], slots * 16)) return s;
-        bt.stage = scr<uint2>(SC_MAP_STAGE); bt.side = (uint32_t *)(bt.stage + slots); bt.slots = (int64_t)slots;          // [packed record x slots][side word x 2 slots]
+        if (int s = phz_reserve(ctx, S[SC_MAP_STAGE], slots * (narrow ? 4 : 16))) return s;
+        bt.stage = scr<uint2>(SC_MAP_STAGE); bt.slots = (int64_t)slots;
+        bt.side = narrow ? nullptr : (uint32_t *)(bt.stage + slots);        // general form: [packed record x slots][side word x 2 slots]; narrow form: [word x slots]
         bt.slot_cap = M.slot_cap;
         OvfArea *h_ov = tab.ovf(M.tab_host), *d_ov = tab.ovf(M.tab);
         h_ov->tile_first = scr<uint32_t>(SC_MAP_TILE_OVF); h_ov->cursor = scal.dev_cursor(ctx->scalars); h_ov->base = (long long)base_slots; h_ov->cap = (long long)M.ovf_cap;
@@ -1238,6 +1307,13 @@ struct MapSubmission {
     }
     template <int B, int R> void launch_k_map(const MapBatch &bt) const {
         const dim3 grid((unsigned)ntiles), block(B);
+        if constexpr (B * R <= STAGE4_MAX_TILE_READS) {
+            if (narrow) {
+                if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true, true>), grid, block, knobs.dyn_lds, sm, bt);
+                else hipLaunchKernelGGL((k_map<B, R, false, false, true>), grid, block, knobs.dyn_lds, sm, bt);
+                return;
+            }
+        }
         if (bt.dbg) hipLaunchKernelGGL((k_map<B, R, true>), grid, block, knobs.dyn_lds, sm, bt);
         else if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true>), grid, block, knobs.dyn_lds, sm, bt);
         else hipLaunchKernelGGL((k_map<B, R, false>), grid, block, knobs.dyn_lds, sm, bt);
@@ -1272,7 +1348,8 @@ struct MapSubmission {
         c.tile_w0 = bt.tile_w0;
         c.slot_cap = bt.slot_cap; c.tile_reads = tile_reads; c.ntiles = ntiles; c.tile_ovf = scr<const uint32_t>(SC_MAP_TILE_OVF);
         const dim3 cgrid((unsigned)((ntiles + 4 * CT - 1) / (4 * CT)));
-        if (text_planes) hipLaunchKernelGGL(k_compact<true>, cgrid, dim3(256), 0, sm, c);
+        if (narrow) hipLaunchKernelGGL((k_compact<false, true>), cgrid, dim3(256), 0, sm, c);
+        else if (text_planes) hipLaunchKernelGGL(k_compact<true>, cgrid, dim3(256), 0, sm, c);
         else hipLaunchKernelGGL(k_compact<false>, cgrid, dim3(256), 0, sm, c);
         PHZ_HIP(ctx, hipGetLastError());
         PHZ_HIP(ctx, hipStreamSynchronize(sm));
@@ -1299,6 +1376,7 @@ struct MapSubmission {
     // ---- timing; calls per shard, PHZ_E_CAPACITY when a shard's buffers were too small for them (its first `cap` calls are in place)
     int results() {
         ctx->last_ms[PHZ_T_MAP] = ms_total; ctx->total_ms[PHZ_T_MAP] += ms_total; ctx->launches[PHZ_T_MAP]++;
+        if (narrow) ctx->counters[PHZ_C_MAP_NARROW]++;
         int st = PHZ_OK;
         for (int k = 0; k < m; k++) {
             const int i = live[(size_t)k];
