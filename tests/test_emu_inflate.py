@@ -2,7 +2,8 @@
 requests) under the host-side HIP emulation, against zlib: stored, fixed-code and dynamic-code blocks, run-length and far matches, alphabets wider than
 the 32 hot symbols, members from one byte to 64 KB, empty members, odd source offsets, several workgroups -- and damaged streams, which must end in a
 status code (from the decoder or from the CRC-32 check against the member's trailer, k_crc32), never in a wrong answer that looks right or an access
-outside the member.  The GPU runs of the same kernel: tests/test_gpu_bamdev.py,
+outside the member.  Every stream here comes from zlib's encoder; the parts of RFC 1951 that zlib never writes (and streams of another encoder) are in
+tests/test_emu_inflate_corners.py.  The GPU runs of the same kernel: tests/test_gpu_bamdev.py, tests/test_gpu_inflate_corners.py,
 tools/inflate_check.py (a whole-genome BAM against zlib)."""
 import ctypes as C
 import zlib

@@ -67,7 +67,8 @@ def _bgzf(payloads, level=6, wbits=-15, strategy=zlib.Z_DEFAULT_STRATEGY):
 
 def test_inflate_matches_zlib_on_every_block_type(ctx):
     """Dynamic-Huffman members (text, long matches, distance-1 runs), fixed-Huffman members (tiny inputs, Z_FIXED), stored members
-    (level 0, incompressible bytes), empty members, several deflate blocks inside one member."""
+    (level 0, incompressible bytes), empty members, several deflate blocks inside one member.  (All written by zlib's encoder; what it never
+    writes: tests/test_gpu_inflate_corners.py.)"""
     rng = np.random.default_rng(7)
     text = ("".join("chr%d\t%d\trs%d\t%s\t%s\t.\tPASS\tAF=%.3f\n" % (rng.integers(1, 23), rng.integers(1, 10 ** 8), rng.integers(1, 10 ** 7), "ACGT"[rng.integers(4)],
                                                                        "ACGT"[rng.integers(4)], rng.random()) for _ in range(5000))).encode()
@@ -90,7 +91,8 @@ def test_inflate_matches_zlib_on_every_block_type(ctx):
 
 
 def test_inflate_reports_damage(ctx):
-    """A member that is not valid DEFLATE, or does not produce ISIZE bytes, sets the status word (the caller then uses zlib)."""
+    """A member that is not valid DEFLATE, or does not produce ISIZE bytes, sets the status word (the caller then uses zlib).  (Each kind of invalid
+    stream with the status code it must end in: tests/test_gpu_inflate_corners.py.)"""
     payload = b"the quick brown fox jumps over the lazy dog " * 500
     good = _bgzf([payload])
     tab, _ = _members(good)
