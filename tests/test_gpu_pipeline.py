@@ -674,7 +674,8 @@ def test_four_ranks_from_bams_equal_one_rank(tmp_path):
 
 def test_cli_fatal_error_waits_for_the_prefetch(tmp_path):
     """A fatal_error raised while the BAM prefetch is running (here: the sample is not in the VCF, found right after the prefetch was started)
-    leaves main() only when that thread is done -- no GPU work of ours is in flight when the interpreter goes down."""
+    leaves main() only when that thread and every other helper thread of the run (they are all named phz-*) is done -- no GPU work of ours is
+    in flight when the interpreter goes down."""
     import gzip, threading
     from phaser_amd import bamio, phaser, synth
     v, gs, ge, w = synth.make_variants("chr22", 1, 3_000_000, 300, 201, n_genes=20)
@@ -687,7 +688,7 @@ def test_cli_fatal_error_waits_for_the_prefetch(tmp_path):
     with pytest.raises(SystemExit):
         phaser.main(["--vcf", vcfgz, "--bam", bam, "--sample", "NOT_THERE", "--mapq", "255", "--baseq", "10", "--paired_end", "1", "--o", str(tmp_path / "o"),
                      "--threads", "2"])
-    assert not any(t.name == "phz-bam-prefetch" and t.is_alive() for t in threading.enumerate())
+    assert not [t.name for t in threading.enumerate() if t.name.startswith("phz-") and t.is_alive()]
 
 
 @pytest.mark.parametrize("backend,world", [("gloo", 2), ("nccl", 2), ("gloo", 3)])
