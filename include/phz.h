@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_COUNT = 12 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_COUNT = 14 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -813,6 +813,36 @@ int phz_binom_test(phz_ctx *ctx, int64_t n_tests, const int32_t *a, const int32_
  * (1-based) gets min(1, min over ranks s >= r of p_(s) * (m / s)), the operations in exactly that order; NaN cells stay NaN.  Tied p-values receive the same
  * q.  At most 2^31 - 1 cells; qvalue must not overlap pvalue.  The kernels (compaction, two sorts, the walk) are timed into PHZ_T_BH. */
 int phz_bh_adjust(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const double *pvalue, double *qvalue, int64_t *n_tested, int space);
+
+/* K_bbfit and K_bbtest (phaser_amd/ae_betabinom.py): the same test against a beta-binomial null, for read counts that are overdispersed against a binomial.  With null mean p0 and
+ * overdispersion rho: alpha = p0 (1 - rho) / rho, beta = (1 - p0)(1 - rho) / rho, pmf(i) = C(n, i) B(i + alpha, n - i + beta) / B(alpha, beta), variance
+ * n p0 (1 - p0)(1 + (n - 1) rho).  Domain: PHZ_BB_RHO_MIN <= rho <= m / (1 + m) with m the smaller of p0 and 1 - p0, which keeps alpha, beta >= 1: there
+ * pmf(i+1) / pmf(i) = (n - i)(i + alpha) / ((i + 1)(n - i - 1 + beta)) does not increase with i, the pmf is unimodal (uniform at p0 = 0.5, rho = 1/3: every
+ * p-value is 1).  a, b: row-major matrices of n_rows x n_cols cells [genes, samples], at most 2^31 - 1 of them; a cell is tested under the rule of K_binom
+ * (counts non-negative, a + b >= the larger of min_cov and 1).  All in fp64.
+ *
+ * phz_betabinom_fit: per column the rho that maximises LL = the sum of log pmf(a; a + b, p0, rho) over the column's tested cells, by a fixed search:
+ * PHZ_BB_FIT_CANDIDATES values equally spaced in ln rho over a bracket, first [ln PHZ_BB_RHO_MIN, ln of the upper bound], PHZ_BB_FIT_ROUNDS rounds; after
+ * a round the bracket becomes [x_(j-1), x_(j+1)] clipped to the bracket's ends, j = the first candidate with the largest LL.  rho_out[c] = exp(x_j) of the
+ * last round (kept inside the domain), loglik_out[c] its LL, n_used_out[c] the tested cells; a column without one gets NaN, NaN, 0.  LL is a fixed-shape
+ * sum -- chunks of 256 rows, added in chunk order -- so the bits of both outputs depend on nothing but the inputs: not on the memory space, not on the run.
+ * Timed into PHZ_T_BBFIT.
+ *
+ * phz_betabinom_test: cell (r, c) is tested with rho[c]; a NaN rho[c] leaves the whole column NaN.  pvalue = min(1, the sum of pmf(i) over ALL i in [0, n]
+ * with pmf(i) <= pmf(k) (1 + 1e-7)): binomtest's two-sided rule carried over to this pmf.  No shortcut at the mean (the mode is elsewhere; the rule gives 1
+ * at the mode by itself); a pmf(k) that underflows gives 0.  log pmf is taken through lgamma, a tail is summed outward from its start index until the terms
+ * fall below 1e-18 of the sum: O(n) terms where rho is large.  Timed into PHZ_T_BBTEST.
+ *
+ * PHZ_E_ARG with a phz_last_error text: p0 not strictly inside the unit interval, more than 2^31 - 1 cells, and for PHZ_HOST inputs an a + b beyond int32
+ * or a non-NaN rho outside the domain (with PHZ_DEVICE the sums are the caller's guarantee and a column whose rho lies outside the domain comes back NaN).
+ * An argument error leaves the outputs untouched. */
+#define PHZ_BB_RHO_MIN 1e-6
+#define PHZ_BB_FIT_CANDIDATES 64
+#define PHZ_BB_FIT_ROUNDS 4
+int phz_betabinom_fit(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, int32_t min_cov, double *rho_out,
+                      double *loglik_out, int64_t *n_used_out, int space);
+int phz_betabinom_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, const double *rho, int32_t min_cov,
+                       double *pvalue, int space);
 
 /* The text of an expression matrix as phaser_expr_matrix writes it -- a header line "#contig start stop name <samples...>", then one row per gene: four
  * leading columns and one aCount|bCount cell per sample, tab-separated -- parsed with host threads.  Lines end in \n or \r\n; empty lines are skipped.

@@ -47,6 +47,10 @@ enum PhzScratch {
     // two column-key buffers of the sort by column, the sorts' digit table, the scans' temporary
     SC_BH_POS = 0, SC_BH_COL_COUNT = 1, SC_BH_COL_OFF = 2, SC_BH_KEY0 = 3, SC_BH_KEY1 = 4, SC_BH_CELL0 = 5, SC_BH_CELL1 = 6, SC_BH_CKEY0 = 7, SC_BH_CKEY1 = 8,
     SC_BH_SORT_COUNT = 9, SC_BH_SCAN_TMP = 10,
+    // K_bbfit (phz_betabinom_fit): candidate table, per-chunk sums of every (column, candidate), per-chunk tested cells of every column
+    SC_BB_CAND = 0, SC_BB_PARTIAL = 1, SC_BB_USED = 2,
+    // K_bbtest (phz_betabinom_test): per-column parameters, wave-tier flag of every cell, its exclusive scan, the listed cells, the scan's temporary
+    SC_BB_COLPAR = 3, SC_BB_FLAG = 4, SC_BB_POS = 5, SC_BB_LIST = 6, SC_BB_SCAN_TMP = 7,
     SC_COUNT = 24
 };
 
