@@ -1468,6 +1468,7 @@ struct TallyPass {
         ctx->counters[PHZ_C_FAR_LINES] += (int64_t)h_counters[12]; ctx->counters[PHZ_C_DIRTY_LISTS] += n_dirty;
         if (profiling) { if (int s = profile_report()) return s; }
         n_complete = (int64_t)grid_t * TL; nt = (int64_t)(h_counters[10] >> 32); n_spill = (int64_t)(h_counters[10] & 0xFFFFFFFFull);
+        ctx->counters[PHZ_C_SPILL_LINES] += n_spill; ctx->counters[PHZ_C_SPILL_QNAMES] += nt;
         return PHZ_OK;
     }
     // PHZ_TALLY_PROFILE: lifetimes and start times of the workgroups of k_line and k_tile, from their cycle stamps (a blocking copy of its own)

@@ -278,6 +278,11 @@ class EmuContext:
             raise self._lib.PhzError(st, (self.lib.phz_last_error(self.h) or b"").decode() or self.lib.phz_strerror(st).decode())
         return st
 
+    def counter(self, slot):
+        v = ctypes.c_int64()
+        self.check(self.lib.phz_get_counter(self.h, slot, ctypes.byref(v)))
+        return v.value
+
     def __del__(self):
         try:
             self.lib.phz_ctx_destroy(self.h)

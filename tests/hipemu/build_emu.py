@@ -36,7 +36,7 @@ def _build_locked(verbose, tally_tile, row_wave_min, stat_n=None):
     LIB = os.path.join(OUT, "libphz_emu%s.so" % tag)
     variant_defs = {}
     if tally_tile:
-        variant_defs["phz_tally.hip"] = ["-DPHZ_TALLY_TILE=%d" % tally_tile, "-DPHZ_RL_STAGE=8"]      # + a tiny read-list stage: the fallback of k_rl_sort
+        variant_defs["phz_tally.hip"] = ["-DPHZ_TALLY_TILE=%d" % tally_tile]
     if row_wave_min is not None:
         variant_defs["phz_rowsdev.hip"] = ["-DPHZ_ROW_WAVE_MIN=%d" % row_wave_min]
     if stat_n is not None:

@@ -64,7 +64,9 @@ inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
 }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(b->t - a->t); return hipSuccess; }
-template <class T> inline hipError_t hipMalloc(T **p, size_t n) { *p = (T *)malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+// device memory arrives filled with 0xA5 and never with the zero pages a large malloc hands out: a kernel that relies on a buffer nobody cleared (a hash table
+// whose empty slots are zeros, a cursor array) fails on every run here, not on the runs where the allocator happens to recycle dirty memory
+template <class T> inline hipError_t hipMalloc(T **p, size_t n) { *p = (T *)malloc(n ? n : 1); if (*p) memset((void *)*p, 0xA5, n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 template <class T> inline hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) { *p = (T *)malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }

@@ -90,61 +90,22 @@ def test_tally_kernels_reproduce_the_gpu_fixture(case, tile):
         assert (int(sz.noise_match), int(sz.noise_mismatch)) == want["noise"] and int(sz.n_kept) == want["n_kept"]
 
 
+# The synthetic inputs live in tests/tally_inputs.py (one named builder each); what K_tally must compute on them is tests/tally_restatement.py's business: EVERY array
+# of phz_tally_fetch and every field of phz_tally_sizes, plus the deltas of the work counters against what the input promises (a far-line input that met no far line
+# fails here).  tests/test_tally_limits.py runs the same check on the further designed cases and on the GPU.
+def _check_against_sets(case, tile=0, ctx=None, reps=1):
+    from test_tally_limits import run_case
+    ctx = ctx or EmuContext(emu_library(tile))
+    for rep in range(reps):
+        run_case(ctx, case, tile or 1024)
+    return ctx
+
+
 def test_tally_kernels_on_skewed_synthetic_lines():
     """Read lists of thousands of entries (workgroup bitonic sort, device radix sort), QNAMEs shared by two BAMs (owner = last BAM), dropped
-    lines: against a direct restatement with Python sets / sorts on the same lines."""
-    rng = np.random.default_rng(7)
-    nv = 24; nq = 3000
-    saved = {"tally": {}, "n_qid": {"chrS": nq}}
-    lines = []
-    for b in range(2):
-        n = 30000 if b == 0 else 7000
-        var = np.sort(rng.choice(nv, size=n, p=np.array([0.55, 0.2] + [0.25 / 22] * 22)))          # variant 0: thousands of lines
-        qid = rng.integers(0, nq, size=n)
-        cls = rng.choice([0, 1, 2, 255], size=n, p=[0.45, 0.4, 0.1, 0.05]).astype(np.uint8)
-        lines.append((var.astype(np.int32), qid.astype(np.int32), cls, np.full(n, b, np.int32)))
-    R = {"nv": nv, "line_var": np.concatenate([l[0] for l in lines]), "line_qid": np.concatenate([l[1] for l in lines]), "line_cls": np.concatenate([l[2] for l in lines]),
-         "line_bam": np.concatenate([l[3] for l in lines]), "bam_offsets": [(0, 0, 30000), (1, 30000, 7000)]}
-    _check_against_sets(R, nv, nq, 2)
-
-
-def _check_against_sets(R, nv, nq, nb, tile=0, as16=False):
-    saved = {"tally": {"chrS": R}, "n_qid": {"chrS": nq}}
-    ctx = EmuContext(emu_library(tile))
-    got, sz = run_tally(ctx, saved, ["chrS"], nb, as16=as16)
-    var, qid, cls, bam = R["line_var"], R["line_qid"], R["line_cls"], R["line_bam"]
-    kept = cls != 255
-    # per-variant counters
-    vc = np.zeros((nv, 3), np.int64)
-    np.add.at(vc, (var[kept], cls[kept]), 1)
-    assert np.array_equal(got["var_count"].reshape(nv, 3), vc)
-    sets = [[set(), set(), set()] for _ in range(nv)]
-    for v, q, c in zip(var[kept], qid[kept], cls[kept]):
-        sets[v][c].add(int(q))
-    assert np.array_equal(got["var_distinct"].reshape(nv, 3), np.array([[len(s) for s in row] for row in sets]))
-    # read lists in line order per (variant, allele, BAM)
-    rs = got["rl_start"]
-    for v in range(nv):
-        for k in range(2):
-            for b in range(nb):
-                e = (2 * v + k) * nb + b
-                want = qid[kept & (var == v) & (cls == k) & (bam == b)]
-                assert np.array_equal(got["rl_qid"][rs[e]:rs[e + 1]], want), (v, k, b)
-    assert int(rs[-1]) == int((kept & (cls < 2)).sum())
-    # nine cells of every variant pair = sizes of the set intersections (phaser.py:1602-1632)
-    cells = got["cells"].reshape(-1, 9)
-    key = got["ea"].astype(np.int64) * (1 << 32) + got["eb"].astype(np.int64)
-    assert np.all(np.diff(key) > 0)                      # the pair list is in (a, b) order, every pair once
-    seen = {}
-    for i, (a, b2) in enumerate(zip(got["ea"], got["eb"])):
-        seen[(int(a), int(b2))] = cells[i]
-    for a in range(nv):
-        for b2 in range(a + 1, nv):
-            want = [len(sets[a][i] & sets[b2][j]) for i in range(3) for j in range(3)]
-            if sum(want) == 0:
-                assert (a, b2) not in seen
-            else:
-                assert list(seen[(a, b2)]) == want, (a, b2)
+    lines: against the restatement with Python dicts / sets / sorts on the same lines."""
+    import tally_inputs
+    _check_against_sets(tally_inputs.skewed())
 
 
 @pytest.mark.parametrize("tile", [0, 256])
@@ -152,81 +113,43 @@ def test_read_lists_with_far_lines_are_sorted_afterwards(tile):
     """A read spliced over hundreds of het SNPs puts call lines outside the variant window of the tile they arrive in (far lines): their read
     lists are filled through cursors and put into line order afterwards -- a short one in LDS, one of > 4,096 entries by the device radix
     sort -- while every other list is written in place, in order, with no sort.  The AS column travels as the 2-byte plane here."""
-    rng = np.random.default_rng(23)
-    nv = 900; nq = 5000
-    var = [np.zeros(6000, np.int64)]                                   # variant 0: 6,000 lines in a row (six tiles with the same window) ...
-    later = np.sort(rng.integers(500, 560, size=3000))                 # ... then lines of variants 500-559, the windows have moved on ...
-    far0 = rng.choice(3000, size=12, replace=False); later[far0] = 0   # ... with twelve more lines of variant 0 among them (far: list (0, *) > 4,096 entries)
-    far7 = rng.choice(3000, size=5, replace=False); later[far7] = 7    # and five of variant 7, which has no other line (a short dirty list)
-    var.append(later)
-    var.append(np.sort(rng.integers(560, 900, size=2500)))
-    var = np.concatenate(var).astype(np.int32)
-    n = len(var)
-    qid = rng.integers(0, nq, size=n).astype(np.int32)
-    cls = rng.choice([0, 1, 2, 255], size=n, p=[0.5, 0.4, 0.05, 0.05]).astype(np.uint8)
-    R = {"nv": nv, "line_var": var, "line_qid": qid, "line_cls": cls, "line_bam": np.zeros(n, np.int32), "bam_offsets": [(0, 0, n)]}
-    _check_against_sets(R, nv, nq, 1, tile, as16=True)
+    import tally_inputs
+    case = tally_inputs.far_lines()
+    assert case.as16 and case.promise(tile or 1024)["far"] > 0 and case.promise(tile or 1024)["dirty"] > 0
+    _check_against_sets(case, tile)
 
 
 @pytest.mark.parametrize("tile", [0, 256])
 def test_tally_kernels_on_long_groups(tile):
     """QNAMEs with more than 64 distinct (variant, class) items: groups that sit inside one tile (finished in place; their later items come
     from the 64-item look-ahead and, beyond it, from memory) and groups that straddle tiles (spill path)."""
-    rng = np.random.default_rng(11)
-    nv = 160; nq = 60
-    var = []; qid = []
-    for q in range(40):                                   # 40 QNAMEs x 110 lines on 110 different variants, contiguous: tile-local groups
-        v = np.sort(rng.choice(nv, size=110, replace=False))
-        var.append(v); qid.append(np.full(110, q))
-    v2 = rng.integers(0, nv, size=6000); q2 = rng.integers(40, nq, size=6000)      # 20 QNAMEs x ~300 lines spread over everything
-    var.append(v2); qid.append(q2)
-    var = np.concatenate(var).astype(np.int32); qid = np.concatenate(qid).astype(np.int32)
-    n = len(var)
-    cls = rng.choice([0, 1, 2, 255], size=n, p=[0.45, 0.4, 0.1, 0.05]).astype(np.uint8)
-    R = {"nv": nv, "line_var": var, "line_qid": qid, "line_cls": cls, "line_bam": np.zeros(n, np.int32), "bam_offsets": [(0, 0, n)]}
-    _check_against_sets(R, nv, nq, 1, tile)
+    import tally_inputs
+    _check_against_sets(tally_inputs.long_groups(), tile)
 
 
 def test_scan_over_many_tiles():
     """The single-launch scan (look-back over the predecessors' status words) on a read-list table of 13 tiles -- more than one round of eight predecessors --,
     twice on one context (the status words of the first scan must read as stale in the second).  (Until round 6: 100 tiles, 4.5 minutes of fibers since the
     tally's column scan walks every variant block; the GPU suite runs the scan over thousands of tiles.)"""
-    rng = np.random.default_rng(5)
-    nv = 26000; nq = 500; n = 3000
-    var = np.sort(rng.integers(0, nv, size=n)).astype(np.int32); qid = rng.integers(0, nq, size=n).astype(np.int32)
-    cls = rng.choice([0, 1, 2, 255], size=n, p=[0.45, 0.4, 0.1, 0.05]).astype(np.uint8)
-    R = {"nv": nv, "line_var": var, "line_qid": qid, "line_cls": cls, "line_bam": np.zeros(n, np.int32), "bam_offsets": [(0, 0, n)]}
-    saved = {"tally": {"chrS": R}, "n_qid": {"chrS": nq}}
-    ctx = EmuContext(emu_library())
-    for rep in range(2):
-        got, sz = run_tally(ctx, saved, ["chrS"], 1)
-        cnt = np.zeros(nv * 2, np.int64)
-        k = cls < 2
-        np.add.at(cnt, var[k].astype(np.int64) * 2 + cls[k], 1)
-        assert np.array_equal(got["rl_start"], np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32))
-        for e in np.flatnonzero(cnt)[:200]:
-            assert np.array_equal(got["rl_qid"][got["rl_start"][e]:got["rl_start"][e + 1]], qid[k & (var == e // 2) & (cls == e % 2)])
+    import tally_inputs
+    _check_against_sets(tally_inputs.scan_over_many_tiles(), reps=2)
 
 
 def test_tally_on_empty_and_fully_dropped_input():
-    """No shard at all, a shard without lines, a shard whose lines are all dropped by the AS cutoff: empty results, and the context stays usable."""
-    from phaser_amd import _lib
-    ctx = EmuContext(emu_library())
-    nv = 50; nq = 10
-    empty = {"nv": nv, "line_var": np.zeros(0, np.int32), "line_qid": np.zeros(0, np.int32), "line_cls": np.zeros(0, np.uint8), "line_bam": np.zeros(0, np.int32),
-             "bam_offsets": [(0, 0, 0)]}
-    got, sz = run_tally(ctx, {"tally": {"chrS": empty}, "n_qid": {"chrS": nq}}, ["chrS"], 1)
+    """A shard without lines, a shard whose lines are all dropped by the AS cutoff: empty results, and the context stays usable for a normal call afterwards."""
+    import tally_inputs
+    empty, dropped, live = tally_inputs.empty_dropped_live()
+    ctx = _check_against_sets(empty)
+    got, sz = run_tally(ctx, empty.saved, empty.chrom_list, 1)
     assert int(sz.n_lines) == 0 and int(sz.n_edges) == 0 and int(sz.n_kept) == 0 and not got["var_count"].any() and not got["rl_start"].any()
-    n = 300
-    rng = np.random.default_rng(2)
-    dropped = {"nv": nv, "line_var": np.sort(rng.integers(0, nv, n)).astype(np.int32), "line_qid": rng.integers(0, nq, n).astype(np.int32),
-               "line_cls": np.full(n, 255, np.uint8), "line_bam": np.zeros(n, np.int32), "bam_offsets": [(0, 0, n)]}
-    got, sz = run_tally(ctx, {"tally": {"chrS": dropped}, "n_qid": {"chrS": nq}}, ["chrS"], 1)
-    assert int(sz.n_lines) == n and int(sz.n_kept) == 0 and int(sz.n_edges) == 0 and not got["var_count"].any() and int(got["rl_start"][-1]) == 0
+    _check_against_sets(dropped, ctx=ctx)
+    got, sz = run_tally(ctx, dropped.saved, dropped.chrom_list, 1)
+    n = dropped.n_lines
+    assert int(sz.n_lines) == n == 300 and int(sz.n_kept) == 0 and int(sz.n_edges) == 0 and not got["var_count"].any() and int(got["rl_start"][-1]) == 0
     assert np.all(got["var_first"] == -1) and np.all(got["line_cls"][:n] == 255)
     # ... and a normal call afterwards
-    live = dict(dropped); live["line_cls"] = rng.choice([0, 1, 2], size=n).astype(np.uint8)
-    got, sz = run_tally(ctx, {"tally": {"chrS": live}, "n_qid": {"chrS": nq}}, ["chrS"], 1)
+    _check_against_sets(live, ctx=ctx)
+    got, sz = run_tally(ctx, live.saved, live.chrom_list, 1)
     assert int(sz.n_kept) == n and int(got["var_count"].sum()) == n
 
 
