@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_COUNT = 14 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_COUNT = 16 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -845,6 +845,40 @@ int phz_betabinom_fit(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_
                       double *loglik_out, int64_t *n_used_out, int space);
 int phz_betabinom_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, const double *rho, int32_t min_cov,
                        double *pvalue, int space);
+
+/* K_blnfit and K_blntest (phaser_amd/ae_outlier.py): per gene, how much the allelic ratio varies in the population, and which samples are outliers against
+ * that.  With null ratio p0 and mu0 = logit(p0):
+ *   x ~ N(mu0, s^2), and k | x ~ Binomial(n, sigma(x)), where sigma is the logistic function;
+ *   pmf(k; n, s) = C(n, k) * the integral over x of sigma(x)^k (1 - sigma(x))^(n-k) phi((x - mu0) / s) / s.
+ * Domain: PHZ_BLN_S_MIN = 1e-3 <= s <= PHZ_BLN_S_MAX = 2.  There is no technical overdispersion term.  a, b: row-major matrices of n_rows x n_cols cells
+ * [genes, samples], at most 2^31 - 1 of them; a cell is tested under K_binom's rule: both counts non-negative and n = a + b >= max(min_cov, 1).  All in fp64.
+ *
+ * phz_bln_fit (K_blnfit) works per row, that is per gene.  It finds the s that maximises LL(s) = the sum of log pmf(a; a + b, s) over the row's tested cells.
+ * The search is K_bbfit's, restated: G = PHZ_BLN_FIT_CANDIDATES = 64 candidates equally spaced in ln s; the first bracket is [ln S_MIN, ln S_MAX]; there are
+ * R = PHZ_BLN_FIT_ROUNDS = 4 rounds; after each round the bracket becomes [x_(j-1), x_(j+1)] clipped to the bracket's ends, where j is the first candidate
+ * with the largest LL; the result is exp(x_j) of the last round, kept inside the domain.  Outputs per row: s_out; loglik_out at that s; loglik_min_out =
+ * LL(S_MIN), which is candidate 0 of round one and stands in for the binomial-like likelihood a user compares against; n_used_out.  A row with fewer than
+ * min_samples tested cells gets NaN, NaN, NaN and its n_used.  The cells of a row are added in ascending column order in one fixed association (the integral
+ * parts per candidate; the log C(n, k) parts once per row, split over 64 lanes by the column index alone and combined by a fixed butterfly).  There is no
+ * floating-point atomic.  The bits do not depend on the grid, on PHZ_HOST / PHZ_DEVICE or on the run.  Timed into PHZ_T_BLNFIT.
+ *
+ * phz_bln_test (K_blntest) tests cell (r, c) with s[r].  A NaN s[r] leaves the row NaN.  Untested cells are NaN.  lower = P(X <= k), upper = P(X >= k), and
+ * the p-value is min(1, 2 min(lower, upper)).  A tail that underflows gives 0.  Timed into PHZ_T_BLNTEST.
+ *
+ * Argument errors of both return PHZ_E_ARG with a phz_last_error text and leave the outputs untouched: p0 not strictly inside (0, 1); more than 2^31 - 1
+ * cells; min_samples < 1; for host inputs, a + b beyond int32, or a non-NaN s outside the domain (with PHZ_DEVICE the sums are the caller's guarantee and a
+ * row whose s lies outside the domain comes back NaN).
+ *
+ * The integrals are Gauss-Hermite rules of PHZ_BLN_Q nodes (a build macro, 32) centred at the mode of the log-concave integrand and scaled by its curvature
+ * there; how the tails are taken (a direct sum of the pmf for n <= PHZ_BLN_SUM_N, two integral forms above) is described in phz_aebln.hip. */
+#define PHZ_BLN_S_MIN 1e-3
+#define PHZ_BLN_S_MAX 2.0
+#define PHZ_BLN_FIT_CANDIDATES 64
+#define PHZ_BLN_FIT_ROUNDS 4
+int phz_bln_fit(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, int32_t min_cov, int32_t min_samples, double *s_out,
+                double *loglik_out, double *loglik_min_out, int64_t *n_used_out, int space);
+int phz_bln_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, const double *s, int32_t min_cov, double *pvalue,
+                 int space);
 
 /* The text of an expression matrix as phaser_expr_matrix writes it -- a header line "#contig start stop name <samples...>", then one row per gene: four
  * leading columns and one aCount|bCount cell per sample, tab-separated -- parsed with host threads.  Lines end in \n or \r\n; empty lines are skipped.

@@ -20,9 +20,10 @@ CSRC = os.path.join(HERE, "csrc")
 PHZ_OK, PHZ_E_ARG, PHZ_E_HIP, PHZ_E_CAPACITY, PHZ_E_UNSUPPORTED, PHZ_E_NOMEM = 0, -1, -2, -3, -4, -5
 PHZ_HOST, PHZ_DEVICE = 0, 1
 PHZ_T_MAP, PHZ_T_ASHIST, PHZ_T_TALLY, PHZ_T_COMPONENTS, PHZ_T_GENES, PHZ_T_INFLATE, PHZ_T_BAMPACK, PHZ_T_ROWS, PHZ_T_BOOT, PHZ_T_ANNOT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
-PHZ_T_BINOM, PHZ_T_BH, PHZ_T_BBFIT, PHZ_T_BBTEST = 10, 11, 12, 13
-PHZ_T_COUNT = 14
+PHZ_T_BINOM, PHZ_T_BH, PHZ_T_BBFIT, PHZ_T_BBTEST, PHZ_T_BLNFIT, PHZ_T_BLNTEST = 10, 11, 12, 13, 14, 15
+PHZ_T_COUNT = 16
 PHZ_BB_RHO_MIN, PHZ_BB_FIT_CANDIDATES, PHZ_BB_FIT_ROUNDS = 1e-6, 64, 4
+PHZ_BLN_S_MIN, PHZ_BLN_S_MAX, PHZ_BLN_FIT_CANDIDATES, PHZ_BLN_FIT_ROUNDS = 1e-3, 2.0, 64, 4
 PHZ_ANNOT_BOTH, PHZ_ANNOT_FIRST = 1, 2
 PHZ_ANNOT_BATCH_ROWS = 1 << 24
 PHZ_C_LINES, PHZ_C_ITEMS, PHZ_C_PAIR_EVENTS, PHZ_C_EDGES, PHZ_C_FAR_LINES, PHZ_C_DIRTY_LISTS, PHZ_C_PAIR_REDOS, PHZ_C_MAP_NARROW = 0, 1, 2, 3, 4, 5, 6, 7
@@ -356,6 +357,8 @@ SYMBOLS = {
     "phz_bh_adjust": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_betabinom_fit": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_betabinom_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
+    "phz_bln_fit": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "phz_bln_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
     "phz_aematrix_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "phz_aetest_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),

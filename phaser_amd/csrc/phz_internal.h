@@ -51,6 +51,8 @@ enum PhzScratch {
     SC_BB_CAND = 0, SC_BB_PARTIAL = 1, SC_BB_USED = 2,
     // K_bbtest (phz_betabinom_test): per-column parameters, wave-tier flag of every cell, its exclusive scan, the listed cells, the scan's temporary
     SC_BB_COLPAR = 3, SC_BB_FLAG = 4, SC_BB_POS = 5, SC_BB_LIST = 6, SC_BB_SCAN_TMP = 7,
+    // K_blntest (phz_bln_test): 1 / s per row, NaN where the row is not tested (K_blnfit keeps everything in registers)
+    SC_BLN_ROWPAR = 0,
     SC_COUNT = 24
 };
 
