@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_COUNT = 16 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_CISSCAN = 16, PHZ_T_COUNT = 17 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -453,6 +453,14 @@ int phz_vcf_lookup(const char *path, int64_t n_keys, const char *const *contig, 
  * for (a CADD table has none that names samples).  *contigs_out as phz_vcf_lookup.  Both buffers are released with phz_buf_free. */
 int phz_tabix_lines(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_cols, const int32_t *cols,
                     int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
+
+/* phaser_amd.cis_scan's reader: every record of a bgzipped VCF inside one of the regions (contig[k], lo[k] <= POS <= hi[k], 1-based, inclusive), once, in file
+ * order, through the .tbi reader of phz_vcf_lookup (use_index and <path>.tbi) or a scan of the whole file.  *out: one line per record,
+ * "CHROM\tPOS\tID\tREF\tALT\tgi\tcodes\n", gi = the index of GT in FORMAT (-1: none, every code is '0') and codes = one character per sample, '0' + the
+ * class (0 skip, 1 het, 2 hom: phaser_amd.cis_var's _classify and its phased test; a GT without '|', a missing sample and texts such as 0|10 are 0) + 4 when
+ * the alternative allele of a het is on haplotype 2 (GT 0|1).  *contigs_out as phz_vcf_lookup.  Both buffers are released with phz_buf_free. */
+int phz_vcf_region_classes(const char *path, int64_t n_regions, const char *const *contig, const int64_t *lo, const int64_t *hi, int32_t n_samples,
+                           const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
 
 /* whole BGZF file -> buffer owned by the library (release it with phz_buf_free and nothing else: a large text is an anonymous mapping, not a malloc'd block);
  * PHZ_E_UNSUPPORTED when the file is plain gzip */
@@ -879,6 +887,44 @@ int phz_bln_fit(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, 
                 double *loglik_out, double *loglik_min_out, int64_t *n_used_out, int space);
 int phz_bln_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, const double *s, int32_t min_cov, double *pvalue,
                  int space);
+
+/* K_cisscan (phaser_amd/cis_scan.py): ASE-based cis mapping.  Every variant of a gene's window is tested for "the gene's |aFC| is larger in the variant's
+ * heterozygotes than in its homozygotes", and the best variant of the gene gets a permutation p-value that accounts for having looked at all of them.
+ *
+ * Inputs.  cls[n_vars][n_samples]: the class of (variant, sample), 0 skip, 1 het, 2 hom.  Gene g owns positions [g_off[g], g_off[g + 1]) of the per-position
+ * arrays, one position per covered sample, n = their number: covered[] = the samples in ascending sample index; order[] = the sample at each position of the
+ * ascending |aFC| order; [run_first[p], run_last[p]] = the positions (gene-local) that tie with position p.  Its variants are the rows [v_lo[g], v_hi[g]) of cls;
+ * its pairs follow those of gene g - 1 in the per-pair outputs.  subseq[g] selects its random stream.
+ *
+ * Per pair: n_het and n_hom count the gene's covered samples of class 1 and 2, and
+ *   u2 = the sum over (het i, hom j) of 2 [|aFC_i| > |aFC_j|] + [|aFC_i| = |aFC_j|].
+ * With D = u2 - n_het n_hom, T = D^2 / (n_het n_hom (n_het + n_hom + 1)) is 3 z^2 of the rank-sum test (scipy.stats.ranksums).  A pair is testable when
+ * n_het >= min_het and n_hom >= min_hom (both minima at least 1).  Two T are compared exactly, as rationals, by a 128-bit cross product.
+ * Per gene: best_v = the testable variant (row of cls) with the largest T, the first among equals, -1 when none is testable.
+ *
+ * Permutations.  Replicate b of gene g sorts i = 0 .. n - 1 ascending by (w(b, i), i), where w(b, i) is word (b n + i) mod 4 of Philox4x32-10 at counter
+ * q = (b n + i) / 4, subsequence subseq[g], key seed (phz_bootstrap_medians' indexing); position p is then held by sample covered[ord_b[p]], while tie runs stay
+ * on positions and classes on samples.  exceed[g] = the number of b < n_perm whose largest T over the testable variants is >= the observed T of best_v (0 when
+ * best_v is -1).  n_perm = 0 computes no replicate.
+ *
+ * All results are integers: they do not depend on the grid, the space or the run.  Host inputs are checked before any launch; PHZ_E_ARG comes with a
+ * phz_last_error text and leaves the outputs untouched: offsets not ascending, a gene with more positions than n_samples, a sample index >= n_samples, a class
+ * above 2, a variant range outside [0, n_vars], run bounds that are not runs, a negative n_perm, a minimum below 1, more than 2^31 - 1 pairs.  With PHZ_DEVICE
+ * the per-gene arrays are read back and checked, the others are the caller's guarantee (indices are clamped, nothing is read out of bounds).  n_samples above
+ * PHZ_CISSCAN_MAX_S gives PHZ_E_UNSUPPORTED.  The three kernels are timed together into PHZ_T_CISSCAN. */
+#define PHZ_CISSCAN_MAX_S 4096
+typedef struct {
+    int64_t n_genes, n_vars;
+    int32_t n_samples;
+    const uint8_t *cls;
+    const int64_t *g_off;                                   /* [n_genes + 1] */
+    const uint16_t *covered, *order, *run_first, *run_last; /* [g_off[n_genes]] */
+    const int64_t *v_lo, *v_hi;                             /* [n_genes] */
+    const uint64_t *subseq;                                 /* [n_genes] */
+    int32_t min_het, min_hom, n_perm;
+    uint64_t seed;
+} phz_cisscan_in;
+int phz_cis_scan(phz_ctx *ctx, const phz_cisscan_in *in, int32_t *n_het, int32_t *n_hom, int64_t *u2, int32_t *best_v, int32_t *exceed, int space);
 
 /* The text of an expression matrix as phaser_expr_matrix writes it -- a header line "#contig start stop name <samples...>", then one row per gene: four
  * leading columns and one aCount|bCount cell per sample, tab-separated -- parsed with host threads.  Lines end in \n or \r\n; empty lines are skipped.

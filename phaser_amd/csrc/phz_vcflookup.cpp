@@ -8,7 +8,13 @@
 //
 // phz_tabix_lines (phaser_annotate's CADD table and allele-frequency VCF) is the same lookup with another reduction of a matching line: a caller-chosen
 // list of columns instead of the VCF fields, and no header line to find.
+//
+// phz_vcf_region_classes (phaser_cis_scan) asks by region instead of by position: the regions of a contig are merged into disjoint intervals, the index path
+// collects the chunks of every interval's bins, and a matching line is reduced to its five leading fields, the GT index and one class character per sample
+// (class_code: cis_var's _classify).  A record inside several of the caller's regions is reported once, since the lines are scanned once, in file order.
 #include <fcntl.h>
+#include <limits.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
@@ -37,7 +43,26 @@ struct Ctx {
     std::vector<int32_t> scol;             // VCF column of each mapped sample, -1 = absent from the header
     const int32_t *cols = nullptr;         // phz_tabix_lines: the columns to report (-1 = the last one) instead of the VCF fields
     int32_t n_cols = 0;
+    // phz_vcf_region_classes: records inside a region instead of records at a key; per contig the merged [lo, hi] intervals (1-based, inclusive), ascending
+    const int64_t *hi = nullptr;
+    std::unordered_map<std::string, std::vector<std::pair<int64_t, int64_t>>> regions;
 };
+
+// phaser_amd.cis_var's _classify and its phased test on one GT text -> '0' + class (+ 4: the "1" of a het is the second field)
+char class_code(std::string_view gt) {
+    if (gt.find('|') == std::string_view::npos) return '0';
+    const size_t zeros = (size_t)std::count(gt.begin(), gt.end(), '0'), ones = (size_t)std::count(gt.begin(), gt.end(), '1');
+    if (zeros && ones) {
+        int idx = 0;
+        for (size_t a = 0;; idx++) {
+            const size_t b = gt.find('|', a);
+            if (gt.substr(a, b == std::string_view::npos ? std::string_view::npos : b - a) == "1") return idx == 0 ? '1' : (idx == 1 ? '5' : '0');
+            if (b == std::string_view::npos) return '0';              // e.g. 0|10
+            a = b + 1;
+        }
+    }
+    return (zeros == 2 || ones == 2) ? '2' : '0';
+}
 
 // one record line -> output line "key\tCHROM\tPOS\tID\tREF\tALT\tgi\tGT...\n" (GT of a column the line lacks: "\x01")
 void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
@@ -48,7 +73,7 @@ void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
         if (j == std::string_view::npos) { f.push_back(line.substr(i)); break; }
         f.push_back(line.substr(i, j - i)); i = j + 1;
     }
-    out += std::to_string(key);
+    if (!C.hi) out += std::to_string(key);
     if (C.cols) {
         for (int32_t k = 0; k < C.n_cols; k++) {
             const int64_t c = C.cols[k] < 0 ? (int64_t)f.size() - 1 : C.cols[k];
@@ -58,7 +83,7 @@ void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
         out += '\n';
         return;
     }
-    for (int k = 0; k < 5; k++) { out += '\t'; if ((size_t)k < f.size()) out.append(f[(size_t)k]); }
+    for (int k = 0; k < 5; k++) { if (k || !C.hi) out += '\t'; if ((size_t)k < f.size()) out.append(f[(size_t)k]); }
     int gi = -1;
     if (f.size() > 8) {
         std::string_view fmt = f[8];
@@ -72,7 +97,22 @@ void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
         }
     }
     out += '\t'; out += std::to_string(gi);
+    if (C.hi) out += '\t';
     for (int32_t c : C.scol) {
+        if (C.hi) {                                                  // one class character per sample
+            char code = '0';
+            if (gi >= 0 && c >= 0 && (size_t)c < f.size()) {
+                std::string_view v = f[(size_t)c];
+                size_t a = 0; int idx = 0;
+                while (idx < gi && a != std::string_view::npos) { a = v.find(':', a); if (a != std::string_view::npos) a++; idx++; }
+                if (a != std::string_view::npos) {
+                    const size_t b = v.find(':', a);
+                    code = class_code(v.substr(a, b == std::string_view::npos ? std::string_view::npos : b - a));
+                }
+            }
+            out += code;
+            continue;
+        }
         out += '\t';
         if (c < 0 || (size_t)c >= f.size()) { out += '\x01'; continue; }
         if (gi < 0) continue;
@@ -109,8 +149,17 @@ void scan(const Ctx &C, const char *p, const char *e, std::string &out, std::vec
                 const long long pos = strtoll(pos_s.c_str(), &endp, 10);
                 if (!pos_s.empty() && endp && *endp == 0) {
                     chrom_s.assign(chrom);
-                    auto it = C.keys.find(Key{chrom_s, pos});
-                    if (it != C.keys.end()) emit(C, it->second, line, out);
+                    if (C.hi) {
+                        auto rg = C.regions.find(chrom_s);
+                        if (rg != C.regions.end()) {
+                            const auto &iv = rg->second;              // the last interval that starts at or before pos
+                            auto u = std::upper_bound(iv.begin(), iv.end(), std::make_pair((int64_t)pos, INT64_MAX));
+                            if (u != iv.begin() && (u - 1)->second >= pos) emit(C, 0, line, out);
+                        }
+                    } else {
+                        auto it = C.keys.find(Key{chrom_s, pos});
+                        if (it != C.keys.end()) emit(C, it->second, line, out);
+                    }
                 }
             }
         }
@@ -214,7 +263,22 @@ int lookup(Ctx &C, const char *path, int64_t n_keys, const char *const *contig, 
     if (!path || n_keys < 0 || !out || !out_len || !contigs_out || !contigs_len || (n_keys && (!contig || !pos))) return PHZ_E_ARG;
     *out = nullptr; *out_len = 0; *contigs_out = nullptr; *contigs_len = 0;
     const bool want_header = C.cols == nullptr;
-    for (int64_t k = 0; k < n_keys; k++) C.keys.emplace(Key{contig[k], pos[k]}, k);
+    if (C.hi) {
+        for (int64_t k = 0; k < n_keys; k++)
+            if (C.hi[k] >= pos[k]) C.regions[contig[k]].emplace_back(pos[k], C.hi[k]);
+        for (auto &r : C.regions) {
+            auto &iv = r.second;
+            std::sort(iv.begin(), iv.end());
+            size_t m = 0;
+            for (size_t i = 1; i < iv.size(); i++) {
+                if (iv[i].first <= iv[m].second + 1) iv[m].second = std::max(iv[m].second, iv[i].second);
+                else iv[++m] = iv[i];
+            }
+            iv.resize(m + 1);
+        }
+    } else {
+        for (int64_t k = 0; k < n_keys; k++) C.keys.emplace(Key{contig[k], pos[k]}, k);
+    }
     const int nt = std::max(1, std::min(threads, 64));
     std::vector<std::string> contigs;
     std::string result;
@@ -270,9 +334,10 @@ int lookup(Ctx &C, const char *path, int64_t n_keys, const char *const *contig, 
         std::vector<uint32_t> bins;
         for (int64_t k = 0; k < n_keys; k++) {
             auto it = rid.find(contig[k]);
-            if (it == rid.end() || pos[k] < 1) continue;
+            if (it == rid.end() || (C.hi ? C.hi[k] < pos[k] || C.hi[k] < 1 : pos[k] < 1)) continue;
             const TbiRef &R = refs[(size_t)it->second];
-            const int64_t beg = pos[k] - 1, end = pos[k];
+            const int64_t top = (int64_t)1 << 29;                     // the index's coordinate space
+            const int64_t beg = std::min(top - 1, std::max<int64_t>(pos[k], 1) - 1), end = C.hi ? std::min(top, std::max(C.hi[k], beg + 1)) : pos[k];
             const size_t w = (size_t)(beg >> 14);
             const uint64_t min_off = R.ioff.empty() ? 0 : (w < R.ioff.size() ? R.ioff[w] : R.ioff.back());
             reg2bins(beg, end, bins);
@@ -345,4 +410,14 @@ extern "C" int phz_tabix_lines(const char *path, int64_t n_keys, const char *con
     Ctx C;
     C.cols = cols; C.n_cols = n_cols;
     return lookup(C, path, n_keys, contig, pos, 0, nullptr, use_index, threads, out, out_len, contigs_out, contigs_len);
+}
+
+extern "C" int phz_vcf_region_classes(const char *path, int64_t n_regions, const char *const *contig, const int64_t *lo, const int64_t *hi, int32_t n_samples,
+                                      const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out,
+                                      int64_t *contigs_len) {
+    if (n_samples < 0 || (n_samples && !samples) || (n_regions && !hi)) return PHZ_E_ARG;
+    static const int64_t none = 0;
+    Ctx C;
+    C.hi = n_regions ? hi : &none;
+    return lookup(C, path, n_regions, contig, lo, n_samples, samples, use_index, threads, out, out_len, contigs_out, contigs_len);
 }
