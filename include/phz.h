@@ -192,7 +192,8 @@ enum { PHZ_C_LINES = 0, PHZ_C_ITEMS = 1, PHZ_C_PAIR_EVENTS = 2, PHZ_C_EDGES = 3,
        PHZ_C_MAP_NARROW = 7 /* phz_map_reads_batch submissions whose calls were staged as 4-byte words (no text planes, <= 256 records per tile, tables <= 2^20) */,
        PHZ_C_SPILL_LINES = 8 /* kept call lines of QNAMEs whose lines straddle tiles or BAMs (handed from k_tile to k_groups) */,
        PHZ_C_SPILL_QNAMES = 9 /* those QNAMEs: one group each in k_groups */,
-       PHZ_C_COUNT = 10 };
+       PHZ_C_SEG_POOL_REDOS = 10 /* read-set stages (phz_rowsdev_run, phz_hap_counts) redone with a four times larger table pool (the attempt before overflowed it) */,
+       PHZ_C_COUNT = 11 };
 
 /* ---- Raw-byte tier, native: the rows of variant_connections / haplotypes / haplotypic_counts re-ordered and re-labelled the way
  * CPython 3.10 with PYTHONHASHSEED=0 orders the reference's sets of strings (phaser/phaser.py:660-678, :930, :1059, :1086, :1106-1115, :1181-1239).  The str

@@ -28,8 +28,8 @@ PHZ_BLN_S_MIN, PHZ_BLN_S_MAX, PHZ_BLN_FIT_CANDIDATES, PHZ_BLN_FIT_ROUNDS = 1e-3,
 PHZ_ANNOT_BOTH, PHZ_ANNOT_FIRST = 1, 2
 PHZ_ANNOT_BATCH_ROWS = 1 << 24
 PHZ_C_LINES, PHZ_C_ITEMS, PHZ_C_PAIR_EVENTS, PHZ_C_EDGES, PHZ_C_FAR_LINES, PHZ_C_DIRTY_LISTS, PHZ_C_PAIR_REDOS, PHZ_C_MAP_NARROW = 0, 1, 2, 3, 4, 5, 6, 7
-PHZ_C_SPILL_LINES, PHZ_C_SPILL_QNAMES = 8, 9
-PHZ_C_COUNT = 10
+PHZ_C_SPILL_LINES, PHZ_C_SPILL_QNAMES, PHZ_C_SEG_POOL_REDOS = 8, 9, 10
+PHZ_C_COUNT = 11
 
 
 class PhzError(RuntimeError):

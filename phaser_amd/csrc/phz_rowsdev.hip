@@ -44,6 +44,13 @@ constexpr int PH_BRUTE_MAX = 22;               // largest fragment brute-forced 
 #endif
 constexpr int PH_DP_MAXD = 10, PH_DP_MINLEN = 8;   // fragments of >= 8 variants whose pairs span <= 10 variants: dynamic programme instead of brute force
 constexpr int SEG_SMALL = 32, SEG_MID = 256, SEG_LDS = 2048;       // read-set sizes: one thread / one wave (512-slot table) / one workgroup (4096 slots, global pool beyond)
+                                               // (mirrored, with STAT_N and the two pool sizes below, at the top of tests/readset_restatement.py: change both)
+#ifndef PHZ_SEG_POOL_BYTES
+#define PHZ_SEG_POOL_BYTES (12 << 20)          // the row stage's table pool as first reserved (grown fourfold and the stage redone on overflow: PHZ_C_SEG_POOL_REDOS);
+#endif                                         // the emulation tests also build a variant with 64 KB pools, which the designed segments overflow
+#ifndef PHZ_HAP_POOL_BYTES
+#define PHZ_HAP_POOL_BYTES (4 << 20)           // ... and that of phz_hap_counts
+#endif
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
 constexpr unsigned long long NONE64 = ~0ull;
 
@@ -1554,6 +1561,8 @@ __global__ __launch_bounds__(256) void k_blk_stats(int64_t nblocks, BS S) {
 //   MODE 0: segment (block, haplotype, BAM): the haplotype's allele lists of the block's non-blacklisted variants in that BAM; labels written
 //   MODE 1: segment (block, haplotype): all variants, all BAMs; count only (reads_hap_a / reads_hap_b of haplotypes.txt)
 //   MODE 2: segment = one (variant, allele, BAM) list; count only (singleton rows when there are several BAMs)
+// Tested directly by tests/test_readset_limits.py (designed segments on both sides of every threshold, huge and blacklisted blocks, colliding ids, pool growth;
+// against tests/readset_restatement.py, emulation and GPU).
 struct SG {
     int64_t nseg; int nb;
     const uint32_t *mem_s, *blk_mstart, *blk_len; const uint8_t *v_alle, *black;
@@ -2492,7 +2501,7 @@ struct Pass {
         // (phased variants and the blocks whose gwStat text the table does not hold are read with the next wait)
         const size_t nlist = std::max((size_t)(nblocks + 1) * 2 * nb, NRL) * 4 + 4;          // (0 bytes: a buffer this pass does not use; the pool keeps what an earlier pass grew it to)
         if (int s = reserve_all(ctx, {{h->labels, NR * 4}, {h->seg_ns, (size_t)(nblocks + 1) * 2 * nb * 4}, {h->big_list, nlist}, {h->big_list2, nlist}, {h->blk_cnt, need_all ? (size_t)(nblocks + 1) * 2 * 4 : 0},
-                                      {h->single_n, nb > 1 || read_ids ? NRL * 4 : 0}, {h->isf0, read_ids ? NR : 0}, {h->isf2, read_ids ? NR : 0}, {h->pool, h->pool.cap ? 0 : (size_t)12 << 20},
+                                      {h->single_n, nb > 1 || read_ids ? NRL * 4 : 0}, {h->isf0, read_ids ? NR : 0}, {h->isf2, read_ids ? NR : 0}, {h->pool, h->pool.cap ? 0 : (size_t)PHZ_SEG_POOL_BYTES},
                                       {h->lab_e, (size_t)(nmem + 1) * 2 * nb * 4}, {h->huge_list, ((size_t)(nmem / (STAT_N + 1) + 2) * 2 * (size_t)nb + 16) * 4},
                                       {h->its, (NR + 1) * 4}, {h->piece_dst, NRL * 8}, {h->big_blk, (size_t)(nblocks + 1) * 4}})) return s;
         h_cc.assign(lay.n32(), 0u);
@@ -2544,6 +2553,7 @@ struct Pass {
                 return PHZ_OK;
             }
             if (attempt == 3) return phz_fail(ctx, PHZ_E_NOMEM, "read-set table pool did not converge");
+            ctx->counters[PHZ_C_SEG_POOL_REDOS]++;
             if (int s = phz_reserve(ctx, h->pool, h->pool.cap * 4)) return s;           // a segment of more than SEG_LDS reads needs 24 B per read: grow and redo
         }
     }
@@ -2843,7 +2853,7 @@ extern "C" int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, i
     DevBuf ns, l1, l2, cnt, pool;
     auto fin = [&](int code) { for (DevBuf *b : {&ns, &l1, &l2, &cnt, &pool}) if (b->p) (void)hipFree(b->p); return code; };
     int st = PHZ_OK;
-    if ((st = reserve_all(ctx, {{ns, (size_t)nseg * 4}, {l1, (size_t)nseg * 4 + 4}, {l2, (size_t)nseg * 4 + 4}, {cnt, 256}, {pool, (size_t)4 << 20}}))) return fin(st);
+    if ((st = reserve_all(ctx, {{ns, (size_t)nseg * 4}, {l1, (size_t)nseg * 4 + 4}, {l2, (size_t)nseg * 4 + 4}, {cnt, 256}, {pool, (size_t)PHZ_HAP_POOL_BYTES}}))) return fin(st);
     for (int attempt = 0;; attempt++) {
         hipError_t e = hipMemsetAsync(cnt.p, 0, 256, sm);
         if (e != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_hap_counts", e));
@@ -2861,6 +2871,7 @@ extern "C" int phz_hap_counts(phz_ctx *ctx, int32_t *counts, int64_t n_counts, i
         if (e != hipSuccess) return fin(phz_fail(ctx, PHZ_E_HIP, "phz_hap_counts", e));
         if (!ovf) break;
         if (attempt == 3) return fin(phz_fail(ctx, PHZ_E_NOMEM, "phz_hap_counts: read-set table pool did not converge"));
+        ctx->counters[PHZ_C_SEG_POOL_REDOS]++;
         if ((st = phz_reserve(ctx, pool, pool.cap * 4))) return fin(st);           // a list of more than SEG_LDS reads keeps its table in the pool: grow and redo
     }
     hipError_t e = hipMemcpyAsync(counts, ns.p, (size_t)nseg * 4, space == PHZ_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, sm);

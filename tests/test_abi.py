@@ -25,13 +25,13 @@ def test_header_symbols_exported(lib):
 
 
 def test_work_counter_slots_match_the_header():
-    """the PHZ_C_* slots of phz_get_counter: the header's enum, slot by slot, in phaser_amd/_lib.py; ten of them, the two spill counters last"""
+    """the PHZ_C_* slots of phz_get_counter: the header's enum, slot by slot, in phaser_amd/_lib.py; eleven of them, the two spill counters and the read-set pool redos last"""
     from phaser_amd import _lib
     hdr = open(os.path.join(REPO, "include", "phz.h")).read()
     slots = {k: int(v) for k, v in re.findall(r"\bPHZ_C_([A-Z_]+)\s*=\s*(\d+)", hdr)}
-    assert slots.pop("COUNT") == len(slots) == 10 and sorted(slots.values()) == list(range(10))
-    assert (slots["MAP_NARROW"], slots["SPILL_LINES"], slots["SPILL_QNAMES"]) == (7, 8, 9)
-    assert _lib.PHZ_C_COUNT == 10
+    assert slots.pop("COUNT") == len(slots) == 11 and sorted(slots.values()) == list(range(11))
+    assert (slots["MAP_NARROW"], slots["SPILL_LINES"], slots["SPILL_QNAMES"], slots["SEG_POOL_REDOS"]) == (7, 8, 9, 10)
+    assert _lib.PHZ_C_COUNT == 11
     for k, v in slots.items():
         assert getattr(_lib, "PHZ_C_" + k) == v, k
 
