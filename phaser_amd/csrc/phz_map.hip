@@ -38,6 +38,7 @@
 // Slot indices, slot_cap, the overflow area, its cursor and the redo are the same in both.
 #include "phz_internal.h"
 #include "phz_lbound.h"
+#include "phz_leanwalk.h"
 #include "phz_stagepack.h"
 #include <stdlib.h>
 #include <string.h>
@@ -346,9 +347,10 @@ __device__ int walk_read(const MapArgs &a, const VarWin &vw, const CigWin &cw, c
 // Lower bound over the staged window: window_lower_bound<D> of phz_lbound.h, a fully unrolled chain of D halving steps and a closing probe over a
 // window padded with INT_MAX up to 2^D entries -- five issue slots per probe (LDS read with an immediate offset, wait, subtract, shift, and-or), no
 // compare / select pair (its VCC hazard costs an s_nop per probe) and nothing on the scalar unit between probes.  The depth is a template
-// parameter: a tile belongs to one of a few DEPTH CLASSES by its window length (wave-uniform, computed once per tile), and a search picks its class
-// with one scalar if/else.  (Until round 10 the depth was the entry point of a `switch` with fall-through cases: the compiler turned that ladder
-// into scalar compares, branches and 64-bit mask moves BETWEEN the probes, 25-30 scalar instructions per search on the busier port.)
+// parameter: a tile belongs to one of a few DEPTH CLASSES by its window length (wave-uniform, computed once per tile); the bracket search of phase 1a
+// picks its class with one scalar if/else (lds_lower_bound), the lean walker is instantiated once per class (walk_lean<D>).  (Until round 10 the depth
+// was the entry point of a `switch` with fall-through cases: the compiler turned that ladder into scalar compares, branches and 64-bit mask moves
+// BETWEEN the probes, 25-30 scalar instructions per search on the busier port.)
 // Two classes, from the staged window lengths of the whole-genome sample (profiles/r10/kmap_search_ab.txt: 75 % of the tiles stage at most 64 entries, 25 %
 // 65..128, one in a thousand more): D = 7, whose padding is one round of the 128-thread workgroup, and the full window.  (D = 6 saves three quarters of
 // the tiles one probe but sends the fourth quarter through the ten probes and four padding rounds of the full window: the same instruction total, more LDS
@@ -367,64 +369,68 @@ __device__ __forceinline__ int lds_lower_bound(const int32_t *w, int wdepth, int
     return wdepth == WIN_DSMALL ? window_lower_bound<WIN_DSMALL>(w, key) : window_lower_bound<WIN_DMAX>(w, key);
 }
 
-__device__ bool walk_lean(const int32_t *s_vpos, int wlen, int wdepth, int w0, const uint32_t *s_cig, uint32_t c_begin, uint32_t cig_cap,
+// D: the depth class of the tile's window (one instantiation per class, picked once per tile by the caller: no if/else at the search).
+// The position rule of one op -- interval, flags, insertion keys, state update, poison -- is lean_step of phz_leanwalk.h; every per-lane flag is an
+// integer there (a per-lane bool carried round a divergent loop is a lane mask on the scalar unit, three instructions per update and loop level).
+// The trip count is the wave's longest record: lanes whose record has ended walk the neutral word, so the loop's exit is one ballot and no lane
+// leaves early; the hit loop is entered only when some lane of the wave has a het SNP under its run (one LDS read, a compare and a ballot).
+template <int D>
+__device__ bool walk_lean(const int32_t *s_vpos, int wlen, int w0, const uint32_t *s_cig, uint32_t c_begin, uint32_t cig_cap,
                           const CandBuf &cb, uint32_t *s_poison, int j, int pos, uint32_t c0, uint32_t c1, long long cover, int dbg) {
     if (c1 - c_begin > cig_cap) return false;
-    int g = 0, seg_start = 0, cnt = 0, nins = 0; uint32_t r = 0;
-    bool bad = false;
-    int t0 = -1, t1 = -1; uint32_t o0 = 0, o1 = 0, l0 = 0, l1 = 0;      // insertions carried forward inside a later segment
-    uint32_t prev = 0x10u, prev_len = 1;                                // "previous op" of the first op: S-like
-    for (uint32_t k = c0; k < c1; k++) {
-        const uint32_t w = s_cig[k - c_begin];
-        const int len = (int)(w >> 4); const uint32_t op = w & 15, bit = 1u << op;
-        const bool mlike = (bit & 0x181u) != 0;
-        if (__builtin_amdgcn_uicmp(op, OP_I, 32 /* ICMP_EQ */) != 0) {          // the lane mask straight from the compare
-            if (op == OP_I) {
-                bad |= (prev & 0x272u) != 0 || prev_len == 0 || nins == 2;      // after I / S / H / P / G / an empty op; a third insertion
-                nins++;
-                t1 = t0; o1 = o0; l1 = l0; t0 = g - 1 + seg_start; o0 = r; l0 = (uint32_t)(len > 4095 ? 4095 : len);
-            }
-        }
-        bad |= op == OP_G;
-        const bool search = (mlike || op == OP_D) && !(dbg & 64);
-        if (__builtin_amdgcn_ballot_w64(search) != 0) {
-            const int lo = pos + g;
-            bad |= search && (long long)lo + len > cover;                       // the run must lie inside the staged window
-            const int hi = (search && !bad) ? lo + len : lo;
-            int i = lds_lower_bound(s_vpos, wdepth, lo);
-            while (i < wlen && !(dbg & 128)) {
-                const int vp = s_vpos[i];
-                if (vp >= hi) break;
-                uint32_t ioff = 0, ilen = 0;
-                if (seg_start == 0) {           // key = offset of the base before the I: the last base of this op
-                    if (vp == hi - 1 && k + 1 < c1) {
-                        const uint32_t wn = s_cig[k + 1 - c_begin];
-                        if ((wn & 15) == OP_I) { ilen = wn >> 4; ilen = ilen > 4095u ? 4095u : ilen; ioff = r + (mlike ? (uint32_t)len : 0u); }
+    LeanWalk s; lean_init(s);
+    const uint32_t nops = c1 - c0;
+    const uint32_t *cig = s_cig + (c0 - c_begin);
+    for (uint32_t u = 0; __builtin_amdgcn_ballot_w64(u < nops) != 0; u++) {
+        const uint32_t w = u < nops ? cig[u] : LEAN_NEUTRAL;
+        LeanOp o = lean_step(s, w, pos, (dbg & 64) ? 0x7fffffffffffffffll : cover);
+        if (dbg & 64) { o.search = 0; o.hi = o.lo; }
+        if (__builtin_amdgcn_ballot_w64(o.search != 0) != 0) {
+            int i = window_lower_bound<D>(s_vpos, o.lo);
+            // (entries [wlen, 2^D) are INT_MAX, never below hi; i == 2^D == MAP_WIN, one past the array, only when wlen == MAP_WIN: the index wraps, i < wlen decides)
+            int vp = s_vpos[i & (MAP_WIN - 1)];
+            bool hit = i < wlen && vp < o.hi && !(dbg & 128);
+            if (__builtin_amdgcn_ballot_w64(hit) != 0) {
+                while (hit) {
+                    const uint32_t x1 = s.seg_start == 0 ? lean_ins_ahead(o, vp, u + 1 < nops ? cig[u + 1] : LEAN_NEUTRAL) : lean_ins_carried(s, vp, pos);
+                    const int nchars = (int)(o.mlike & 1u) + (int)(x1 & LEAN_INS_MAX);
+                    if (nchars > 0) {
+                        const int slot = s.cnt < 32 ? atomicAdd(cb.n, 1) : (atomicOr(cb.n, 1 << 30), 1 << 30);      // OR, not ADD: thousands of these in one tile must not wrap the counter
+                        if (slot < cb.cap)
+                            cand_put(cb, slot, ((uint32_t)j << 16) | ((uint32_t)(s.cnt | 0x80) << 8) | (nchars == 1 ? 7u : 4u), w0 + i,
+                                     o.mlike ? o.rbase + (uint32_t)(vp - o.lo) : 0xFFFFFFFFu, x1);
+                        s.cnt++;
                     }
-                } else {
-                    const int off = vp - pos;
-                    if (t0 == off) { ioff = o0; ilen = l0; } else if (t1 == off) { ioff = o1; ilen = l1; }
+                    i++;
+                    vp = s_vpos[i & (MAP_WIN - 1)];
+                    hit = i < wlen && vp < o.hi;
                 }
-                const int nchars = (mlike ? 1 : 0) + (int)ilen;
-                if (nchars > 0) {
-                    const int slot = cnt < 32 ? atomicAdd(cb.n, 1) : (atomicOr(cb.n, 1 << 30), 1 << 30);      // OR, not ADD: thousands of these in one tile must not wrap the counter
-                    if (slot < cb.cap)
-                        cand_put(cb, slot, ((uint32_t)j << 16) | ((uint32_t)(cnt | 0x80) << 8) | (nchars == 1 ? 7u : 4u), w0 + i,
-                                 mlike ? (uint32_t)(r + (uint32_t)(vp - lo)) : 0xFFFFFFFFu, ilen > 0 ? ((ioff << 12) | ilen) : 0u);
-                    cnt++;
-                }
-                i++;
             }
         }
-        // (a mask of all ones from bit `op` of a table, by one signed bit-field extract: no compare into VCC and no hazard wait before a select;
-        // written as plain arithmetic the compiler folds it back into that pair)
-        g += len & __builtin_amdgcn_sbfe(0x38D, op, 1u);                          // M D N = X G advance the reference
-        r += (uint32_t)(len & __builtin_amdgcn_sbfe(0x193, op, 1u));              // M I S = X advance the read
-        if (op == OP_N) { seg_start = g; t0 = -1; t1 = -1; }
-        prev = bit; prev_len = (uint32_t)len;
     }
-    if (bad) atomicOr(&s_poison[j >> 5], 1u << (j & 31));
-    return !bad;
+    if (s.bad) atomicOr(&s_poison[j >> 5], 1u << (j & 31));
+    return s.bad == 0;
+}
+
+// one pass of the lean walker over the tile's multi-op list: RPT rounds of the workgroup (the list has at most TILE entries).  -> non-zero when this
+// lane left a record to the general walker.  An integer, and straight-line rounds: the flag is not carried round a divergent loop.
+template <int D, int MAP_BLOCK, int RPT>
+__device__ __forceinline__ uint32_t lean_pass(bool lean_on, int tid, int ncx, int nshort, uint16_t *s_cx, const int32_t *s_vpos, int wlen, int w0,
+                                              const uint32_t *s_cig, uint32_t c_begin, const CandBuf &cb, uint32_t *s_poison, const int32_t *s_pos,
+                                              const uint32_t *s_coff, long long cover, int dbg) {
+    constexpr int TILE = MAP_BLOCK * RPT;
+    uint32_t redo_any = 0;
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+        const int t = k * MAP_BLOCK + tid;
+        if (t < ncx) {
+            const int ts = t < nshort ? t : TILE - 1 - (t - nshort);
+            const int j = s_cx[ts];
+            const bool done = lean_on && walk_lean<D>(s_vpos, wlen, w0, s_cig, c_begin, (uint32_t)(TILE * PHZ_CIG_X2 / 2), cb, s_poison, j, s_pos[j], s_coff[j], s_coff[j + 1], cover, dbg);
+            if (!done) { s_cx[ts] = (uint16_t)(j | 0x8000); redo_any = 1u; }
+        }
+    }
+    return redo_any;
 }
 
 constexpr int MAP_COVER = 65536;   // the staged window holds every het SNP below POS(last read of the tile) + MAP_COVER ...
@@ -675,17 +681,20 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     for (int k = 0; k < RPT; k++) {
         const int j = k * MAP_BLOCK + tid;
         const int lo = __builtin_amdgcn_readlane(bound, 2 * k * GROUP), hi = __builtin_amdgcn_readlane(bound, (2 * k + 1) * GROUP);
-        if (one_[k]) {
-            const int pos = rpos_[k], end = pos + len_[k];
+        {
+            const int pos = rpos_[k], end = (int)((uint32_t)pos + (uint32_t)len_[k]);
             if (hi - lo <= 24) {
-                int below = 0, c = 0;
+                // wave-uniform bounds and every lane of the wave in the loop (one_ is applied afterwards, by a select): the loop's control is a scalar
+                // counter and one branch, no lane mask is saved or restored per entry.  pos <= end: the entries in [pos, end) are those below end less those below pos
+                int below = 0, below_end = 0;
                 for (int e = lo; e < hi; e++) {
                     const int vp = s_vpos[e];
                     below += vp < pos ? 1 : 0;
-                    c += (vp >= pos && vp < end) ? 1 : 0;
+                    below_end += vp < end ? 1 : 0;
                 }
-                if (c <= 8) { fast_[k] = true; base_[k] = lo + below; n_[k] = c; }
-            } else {
+                const int c = below_end - below;
+                if (one_[k] && c <= 8) { fast_[k] = true; base_[k] = lo + below; n_[k] = c; }
+            } else if (one_[k]) {
                 const int base = lds_lower_bound(s_vpos, wdepth, pos);
                 int c = 0;
                 while (base + c < vw.wlen && s_vpos[base + c] < end && c <= 8) c++;
@@ -720,14 +729,10 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     const int ncx = (walk_on && !(a.dbg & 256)) ? nshort + s_nlong : 0;       // dbg 256: multi-op records listed but not walked
     const bool lean_on = complete && !(a.dbg & 32);
     // 1b: the lean walker first (one lane per multi-op record, densely packed); what it declines is redone by the general walker
-    bool redo_any = false;
-    for (int t = tid; t < ncx; t += MAP_BLOCK) {
-        const int ts = t < nshort ? t : TILE - 1 - (t - nshort);
-        const int j = s_cx[ts];
-        const bool done = lean_on && walk_lean(s_vpos, vw.wlen, wdepth, vw.w0, s_cig, cw.c_begin, (uint32_t)CIG, cb, s_poison, j, s_pos[j], s_coff[j], s_coff[j + 1], cover, a.dbg);
-        if (!done) { s_cx[ts] = (uint16_t)(j | 0x8000); redo_any = true; }
-    }
-    const bool redo = __syncthreads_or(redo_any ? 1 : 0) != 0;
+    const uint32_t redo_any = wdepth == WIN_DSMALL
+        ? lean_pass<WIN_DSMALL, MAP_BLOCK, RPT>(lean_on, tid, ncx, nshort, s_cx, s_vpos, vw.wlen, vw.w0, s_cig, cw.c_begin, cb, s_poison, s_pos, s_coff, cover, a.dbg)
+        : lean_pass<WIN_DMAX, MAP_BLOCK, RPT>(lean_on, tid, ncx, nshort, s_cx, s_vpos, vw.wlen, vw.w0, s_cig, cw.c_begin, cb, s_poison, s_pos, s_coff, cover, a.dbg);
+    const bool redo = __syncthreads_or((int)redo_any) != 0;
     // the lean walk was the last reader of s_pos: its words become the per-record call masks (zeroed here, OR-ed after the next barrier);
     // the few records left to the general walker fetch their position again
 #pragma unroll
