@@ -290,22 +290,25 @@ int parse_bam_header(const uint8_t *d, size_t dn, std::vector<std::pair<std::str
     return 0;
 }
 
-// can offset p of the inflated bytes d[0, n) start a record?  -> offset of the next record, 0 when it cannot
-size_t plausible_at(const uint8_t *d, size_t n, size_t p, int n_ref) {
-    if (p + 36 > n) return 0;
+// What stands at offset p of the inflated bytes d[0, n)?  0: a plausible record (*next = offset of the next one);  1: a plausible header whose record
+// reaches past n, or less than a header is left -- more bytes would tell;  2: not a record.
+int record_at(const uint8_t *d, size_t n, size_t p, int n_ref, size_t *next) {
+    if (p + 36 > n) return 1;
     const int32_t bs = rdi32(d + p);
-    if (bs < 32 || bs > (1 << 24) || p + 4 + (size_t)bs > n) return 0;
+    if (bs < 32 || bs > (1 << 24)) return 2;
     const uint8_t *r = d + p + 4;
     const int32_t ref = rdi32(r), pos0 = rdi32(r + 4), l_seq = rdi32(r + 16), nref = rdi32(r + 20);
     const uint32_t l_rn = r[8], n_cig = rd16(r + 12), flag = rd16(r + 14);
     // a QNAME has at least one character (SAM: [!-?A-~]{1,254}; an empty name would make every zero byte a candidate), FLAG has 12
     // defined bits, mate position >= -1
-    if (ref < -1 || ref >= n_ref || nref < -1 || nref >= n_ref || pos0 < -1 || l_seq < 0 || l_rn < 2 || flag >= 4096 || rdi32(r + 24) < -1) return 0;
+    if (ref < -1 || ref >= n_ref || nref < -1 || nref >= n_ref || pos0 < -1 || l_seq < 0 || l_rn < 2 || flag >= 4096 || rdi32(r + 24) < -1) return 2;
     const size_t need = 32 + (size_t)l_rn + 4 * (size_t)n_cig + ((size_t)l_seq + 1) / 2 + (size_t)l_seq;
-    if (need > (size_t)bs) return 0;
-    if (r[32 + l_rn - 1] != 0) return 0;                 // read name is NUL-terminated
-    for (uint32_t k = 0; k + 1 < l_rn; k++) if (r[32 + k] < 33 || r[32 + k] > 126) return 0;
-    return p + 4 + (size_t)bs;
+    if (need > (size_t)bs) return 2;
+    if (p + 4 + (size_t)bs > n) return 1;
+    if (r[32 + l_rn - 1] != 0) return 2;                 // read name is NUL-terminated
+    for (uint32_t k = 0; k + 1 < l_rn; k++) if (r[32 + k] < 33 || r[32 + k] > 126) return 2;
+    *next = p + 4 + (size_t)bs;
+    return 0;
 }
 
 // member table of a BGZF file (nothing inflated)
@@ -572,10 +575,14 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
     //  -1  no record boundary could be PROVEN in members b .. b+7 (records longer than the window, damaged members): the caller must
     //      not guess -- a wrong "past this reference" would silently drop records -- and gives the file to the full, order-agnostic open.
     // The window starts at three members and grows (x4, up to 256 members = 16 MB) while candidate chains run out of data, so records of
-    // tens of kilobytes (long reads, large aux fields) are still chained 12 deep.
+    // tens of kilobytes (long reads, large aux fields) are still chained 12 deep.  What is answered becomes a reference boundary or a piece limit that
+    // nothing downstream can check against a chain from the file's start (that is the point of a restricted open), so 12 headers are not taken at their word:
+    // see the loop.  What no local rule can tell from records -- a run of fakes that ends exactly where its record ends, so that the chain goes on over true
+    // records -- is still taken here; the callers ask probe_from_before, which does not rely on it.
     auto probe = [&](size_t b, uint64_t *uoff, int32_t *ref) -> int {
         std::vector<uint8_t> tmp, ctmp;
         size_t b1 = b;
+        bool doubt = false;                                    // something that began like a record chain was rejected
         for (; b1 < nb && b1 < b + 8; b1++) {
             for (size_t win = 3;; win *= 4) {
                 tmp.clear();                                   // window = members b1 .. b1+win-1
@@ -597,28 +604,76 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
                 const size_t lim = M.blks[b1].isize;
                 bool short_of_data = false;
                 for (size_t p = 0; p < lim; p++) {
+                    // A candidate is taken when its chain is at least 12 records deep AND stays plausible until it leaves the window (or the file): 12 headers
+                    // in a row also occur INSIDE a record (an aux array of arbitrary bytes), and a chain of such fakes that breaks inside the window, on bytes
+                    // that are no header, is proven not to be the record chain.  The scan goes on behind it.  (Coordinate order along the chain is NOT asked
+                    // here, unlike in k_seg_start: a chain that descends is either a fake or an unsorted file, the scan would go on behind true records of the
+                    // latter and answer a boundary that drops records; as it is, the refIDs sampled by the search give an unsorted file away.)
                     size_t q = p; int ok = 0;
-                    while (ok < 12) {
-                        const size_t nx = plausible_at(tmp.data(), tmp.size(), q, n_ref);
-                        if (!nx) {
-                            // out of window with a header that still looks like a record: a larger window may complete the chain
-                            if (ok > 0 || q == p) {
-                                if (q + 36 <= tmp.size()) {
-                                    const int32_t bs = rdi32(tmp.data() + q);
-                                    if (bs >= 32 && bs <= (1 << 24) && q + 4 + (size_t)bs > tmp.size()) short_of_data = true;
-                                } else if (ok > 0) short_of_data = true;
-                            }
+                    bool taken = false;
+                    for (;;) {
+                        size_t nx = 0;
+                        const int what = record_at(tmp.data(), tmp.size(), q, n_ref, &nx);
+                        if (what == 1) {
+                            // out of window with a header that still looks like a record: deep enough, or a larger window may complete the chain.  At the end
+                            // of the file there is no more to come: a record that reaches past it is none, its chain is turned down like a dead end
+                            if (at_eof) { if (ok > 0 || q + 36 <= tmp.size()) doubt = true; }
+                            else if (ok >= 12) taken = true;
+                            else if (q + 36 <= tmp.size() || ok > 0) short_of_data = true;
                             break;
                         }
+                        if (what == 2) { if (ok > 0) doubt = true; break; }
                         ok++; q = nx;
-                        if (at_eof && q + 36 > tmp.size()) { ok = 12; break; }      // the chain ran into the end of the file
+                        if (at_eof && q + 36 > tmp.size()) { taken = true; break; }      // the chain ran into the end of the file
                     }
-                    if (ok >= 12) { *uoff = M.blks[b1].dst + p; *ref = rdi32(tmp.data() + p + 4); return 1; }
+                    if (taken) { *uoff = M.blks[b1].dst + p; *ref = rdi32(tmp.data() + p + 4); return 1; }
                 }
                 if (!short_of_data || at_eof || win >= 256) break;
             }
         }
-        return b1 >= nb ? 0 : -1;
+        return b1 >= nb && !doubt ? 0 : -1;                     // "no record starts here or later" only when nothing record-like was turned down on the way
+    };
+    // probe_from_before(b): what probe(b) is asked for, reached from the member BEFORE b -- the chain from probe(b - 1)'s candidate is walked until it
+    // passes the start of member b, and where it ARRIVES is the answer.  A run of fakes that ends with its record resyncs: its chain goes on over true
+    // records and passes the window test above.  Such a candidate at the start of member b would become a piece limit inside a record, or give the search
+    // the fakes' refID; as the START of a walk it is harmless, the walk leaves the run with the record and arrives on the true chain (it is wrong only
+    // where one run of fakes covers the rest of member b - 1 and the start of b).  Where b - 1 offers nothing to start from, probe(b) answers as before.
+    // Cost: the members of the walk are inflated a second time.  Measured on a 52 MB BAM of 700,000 records (about 870 members), host, medians of 10: the piece
+    // limits of a restricted open 7.8 -> 13.4 ms, the three searches of phz_bam_open_refs with ref_bytes 30 -> 49 ms; the search is logarithmic in the members.
+    auto probe_from_before = [&](size_t b, uint64_t *uoff, int32_t *ref) -> int {
+        if (b <= b0) return probe(b, uoff, ref);
+        uint64_t c = 0; int32_t cref = 0;
+        const int st = probe(b - 1, &c, &cref);
+        if (st < 0) return probe(b, uoff, ref);
+        if (st == 0) return 0;
+        const uint64_t want = M.blks[b].dst;
+        if (c >= want) { *uoff = c; *ref = cref; return 1; }                      // no record starts in member b - 1
+        std::vector<uint8_t> buf, ctmp;
+        size_t next_m = b - 1;                                                    // c lies in member b - 1; buf = members b - 1 .. next_m - 1
+        auto more = [&]() -> bool {
+            if (next_m >= nb || next_m >= b + 256) return false;
+            const size_t old = buf.size();
+            buf.resize(old + M.blks[next_m].isize);
+            if (M.blks[next_m].isize) {
+                const uint8_t *src = M.member(next_m, ctmp);
+                if (!src || !inflate_block(src, M.blks[next_m].csize, buf.data() + old, M.blks[next_m].isize)) { buf.resize(old); return false; }
+            }
+            next_m++;
+            return true;
+        };
+        size_t p = (size_t)(c - M.blks[b - 1].dst);
+        for (;;) {
+            if (M.blks[b - 1].dst + p >= want) {                                  // arrived
+                while (p + 8 > buf.size()) if (!more()) break;
+                if (p + 8 > buf.size()) return next_m >= nb && p == buf.size() ? 0 : -1;      // the chain ended with the file: no record starts in b or later
+                *uoff = M.blks[b - 1].dst + p; *ref = rdi32(buf.data() + p + 4);
+                return 1;
+            }
+            size_t nx = 0; int what;
+            while ((what = record_at(buf.data(), buf.size(), p, n_ref, &nx)) == 1) if (!more()) break;
+            if (what != 0) return -1;                                             // the chain broke or outgrew 256 members: nothing proven
+            p = nx;
+        }
     };
     const int32_t INF = 0x7fffffff;
     bool uncertain = false;
@@ -631,7 +686,7 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
             const size_t m = (lo + hi) >> 1;
             uint64_t u; int32_t ref;
             int32_t key = INF;
-            const int pr = probe(m, &u, &ref);
+            const int pr = probe_from_before(m, &u, &ref);
             if (pr < 0) { uncertain = true; return nb; }
             if (pr > 0) key = ref < 0 ? INF : ref;
             samples.emplace_back(m, key);
@@ -649,6 +704,7 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
             if (line.find("SO:unsorted") != std::string_view::npos || line.find("SO:queryname") != std::string_view::npos) return PHZ_E_UNSUPPORTED;
         }
     }
+    *first_record_out = first_record;          // from here on PHZ_E_UNSUPPORTED means: the header is fine, boundaries could not be proven
     std::vector<size_t> begin_blk((size_t)n_ref + 1, nb);
     std::vector<char> want((size_t)n_ref, 0);
     for (int i = 0; i < n_ref; i++) {
@@ -664,7 +720,6 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
         }
     }
     laps.lap("reference boundary search");
-    *first_record_out = first_record;
     if (uncertain) return PHZ_E_UNSUPPORTED;
     if (!want_pieces) return PHZ_OK;
     // runs of consecutive wanted references -> byte ranges [u_begin, u_end) of the uncompressed stream, cut at record boundaries
@@ -678,8 +733,8 @@ static int bam_plan(BgzfMap &M, const char *const *ref_names, int n_names, int64
         uint64_t u0 = first_record, u1 = total_u; int32_t rr;
         if (uncertain) return PHZ_E_UNSUPPORTED;
         const size_t sb = bs > b0 ? bs - 1 : b0;                  // records of reference i may begin in the member before bs
-        if (sb > b0) { const int pr = probe(sb, &u0, &rr); if (pr < 0) return PHZ_E_UNSUPPORTED; if (pr == 0) u0 = M.blks[sb].dst; }
-        if (be < nb) { const int pr = probe(be, &u1, &rr); if (pr < 0) return PHZ_E_UNSUPPORTED; if (pr == 0) u1 = total_u; }
+        if (sb > b0) { const int pr = probe_from_before(sb, &u0, &rr); if (pr < 0) return PHZ_E_UNSUPPORTED; if (pr == 0) u0 = M.blks[sb].dst; }
+        if (be < nb) { const int pr = probe_from_before(be, &u1, &rr); if (pr < 0) return PHZ_E_UNSUPPORTED; if (pr == 0) u1 = total_u; }
         if (!pieces.empty() && u0 < pieces.back().u1) u0 = pieces.back().u1;       // the member before this run may belong to the previous piece
         if (u1 > u0) pieces.push_back({u0, u1});
         i = j + 1;
@@ -696,7 +751,14 @@ int phz_bam_plan_file(const char *path, const char *const *ref_names, int n_name
     if (int st = M->open(path, true)) { delete M; return st == PHZ_E_UNSUPPORTED ? PHZ_E_ARG : st; }
     laps.lap("member table");
     std::vector<BamPiece> pieces;
-    if (int st = bam_plan(*M, ref_names, n_names, nullptr, 0, true, out->refs, out->head, &out->first_record, pieces, laps)) { delete M; return st; }
+    if (int st = bam_plan(*M, ref_names, n_names, nullptr, 0, true, out->refs, out->head, &out->first_record, pieces, laps)) {
+        // reference boundaries that cannot be proven (see phz_bam_open_refs, which takes the full open then): the whole record stream as ONE piece, from the
+        // true first record to the end of the file -- more to copy and inflate, never lossy; the caller's reference mask still selects the records, and its
+        // record hop refuses a file that is not coordinate-sorted.  (A header that declares another order is refused before any of this.)
+        if (st != PHZ_E_UNSUPPORTED || out->first_record == 0) { delete M; return st; }
+        pieces.clear();
+        if (M->total > out->first_record) pieces.push_back({(uint64_t)out->first_record, (uint64_t)M->total});
+    }
     for (auto &p : pieces) out->pieces.emplace_back(p.u0, p.u1);
     const size_t nb = M->blks.size();
     size_t b = 0;
@@ -736,8 +798,9 @@ int phz_bam_open(const char *path, int threads, phz_bam **out) {
 
 // Chromosome-restricted open (what `samtools view BAM 'chr':` does with the .bai, phaser/phaser.py:1346; here without an index
 // file): the BGZF member table is read from the member headers alone, the members in which the wanted references begin / end are
-// found by binary search (a coordinate-sorted BAM keeps every reference's records contiguous; a probe inflates two members and
-// looks for the first record boundary with the same plausibility chain the parallel record hop uses), and only the members that
+// found by binary search (a coordinate-sorted BAM keeps every reference's records contiguous; a probe inflates a few members, looks
+// for a record boundary with the plausibility chain the parallel record hop uses, followed to the end of what it inflated, and walks
+// from there to the member it was asked about: see probe / probe_from_before in bam_plan), and only the members that
 // hold wanted records are inflated.  The result is a stream cut at record boundaries, i.e. a valid record chain: phz_bam_decode
 // works on it unchanged.  ref_bytes (may be NULL) receives, per reference, the compressed bytes between the members where it and
 // the next reference begin: a proxy of its record count, available before anything is decoded (LPT weights).

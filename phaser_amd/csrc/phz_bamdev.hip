@@ -13,7 +13,14 @@
 //   scan + k_hop<1>   kept-record list (offset, reference, op count, bases, name length)
 //   scans + k_pack    one lane per kept record writes its slots of the shard arrays (normalised CIGAR, 2-bit bases, quals, AS)
 // Anything the device path cannot prove (a member that is not valid DEFLATE, a boundary that does not verify, an unsorted file,
-// 32-bit offsets exceeded) returns PHZ_E_UNSUPPORTED and the caller uses the host path.
+// 32-bit offsets exceeded) returns PHZ_E_UNSUPPORTED and the caller uses the host path.  Reference boundaries that the plan cannot prove are not among
+// them: phz_bam_plan_file then answers the whole record stream as one piece, and the reference mask selects the records here.
+//
+// Tested in tests/test_gpu_bamdev.py (K_inflate against zlib; shards against the host decoder under every filter, on odd records, long reads, damaged
+// members and corrupt streams; the chunked multi-stream pipeline) and in tests/test_gpu_bam_boundaries.py (k_seg_start, k_hop<0> and counting_hop on
+// files with PLANTED fake record chains under chosen segment guesses, against the sequential Python reader: one repair per pass for fakes at
+// consecutive guesses, 7 in a row converge and 8 decline, fakes out of coordinate order are never taken, a dead-end fake chain behind an unclean
+// segment does not fail the file, a record longer than two segments leaves empty segments; members that start on a fake, whole file and restricted, the one-piece plan included).
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <stdint.h>
@@ -136,7 +143,8 @@ struct Filters {
     int n_ref;
 };
 
-// can offset p of d[0, n) start a record?  -> offset of the next record, 0 when it cannot (same test as the host's plausible_at)
+// can offset p of d[0, n) start a record?  -> offset of the next record, 0 when it cannot (same test as the host's record_at);
+// *key = the record's coordinate-sort key (k_seg_start wants the keys of a chain in order, which the host's guesses do not ask)
 __device__ uint64_t plausible(const uint8_t *d, uint64_t n, uint64_t p, int n_ref, uint64_t *key) {
     if (p + 36 > n) return 0;
     const int32_t bs = ldi32(d + p);
