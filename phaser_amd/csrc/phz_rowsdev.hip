@@ -70,6 +70,7 @@ __device__ __forceinline__ int ndigits(unsigned long long v) {
 
 #ifndef PHZ_ROW_WAVE_MIN
 #define PHZ_ROW_WAVE_MIN 16          // block rows of more variants than this are formatted by a wave each (the emulation tests also build a variant with 0)
+                                     // (mirrored in tests/rowtext_inputs.py: change both)
 #endif
 constexpr int ROW_WAVE_MIN = PHZ_ROW_WAVE_MIN;
 
@@ -2569,6 +2570,7 @@ struct Pass {
             if (h_nbig && write) hipLaunchKernelGGL(k_row_wave_write<ROW>, dim3(h_nbig * (unsigned)per_blk), dim3(64), 0, sm, D, (const uint32_t *)h->big_blk.p, per_blk, of, out);
         }
     }
+    // (rows per workgroup and stage bytes per file, with PHZ_ROW_WAVE_MIN, PHZ_HAP_* and PHZ_ASE_* above: mirrored in tests/rowtext_inputs.py: change both)
     void launch_rows(int f, bool write) {
         if (!rows[f]) return;
         switch (f) {
