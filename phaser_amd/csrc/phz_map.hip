@@ -40,6 +40,8 @@
 #include "phz_lbound.h"
 #include "phz_leanwalk.h"
 #include "phz_stagepack.h"
+#include "phz_stageload.h"
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -579,7 +581,7 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t tile = gtile - bt.tile0[si];          // tile index inside the shard
     const int64_t r0 = tile * TILE;
-    const int nr = (int)((a.n - r0) < TILE ? (a.n - r0) : TILE);
+    const int nr = stage_tile_records(a.n, r0, TILE);
 
     // ---- coalesced streaming loads: pos / seq_off / cigar_off slices, the het-SNP window and the tile's CIGAR words into LDS.
     //      Every load a lane needs (the window and the CIGAR words almost always fit one and three rounds of the workgroup) is
@@ -590,10 +592,33 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     const bool complete = (tw.y >> 30) & 1;
     CigWin cw;
     cw.g = a.cigar; cw.lds = s_cig; cw.c_begin = (uint32_t)tw.z; cw.cap = CIG;
-    uint32_t cnt_w = (uint32_t)tw.w;
-    if (cnt_w > (uint32_t)CIG) cnt_w = CIG;
+    const uint32_t cnt_w = stage_cigar_words((uint32_t)tw.w, (uint32_t)CIG);
     int rpos_[RPT];
     uint32_t soff_[RPT], coff_[RPT];
+    uint32_t cg[3] = {0, 0, 0};
+#ifndef PHZ_MAP_FLAT_STAGE
+    // One bounds-checked descriptor per slice, built from the tile's uniform values (phz_stageload.h): a lane past a slice's end loads 0, so no load
+    // below sits under a lane mask or computes a 64-bit address.  The window's descriptor ends at the table's end: entries past it are padding.
+    const auto d_pos = PHZ_STAGE_RSRC(a.pos + r0, nr), d_soff = PHZ_STAGE_RSRC(a.seq_off + r0, nr);
+    const auto d_coff = PHZ_STAGE_RSRC(a.cigar_off + r0, stage_coff_words(nr));
+    const uint32_t wlive = stage_window_words(vw.wlen, a.nv, vw.w0);
+    const auto d_win = PHZ_STAGE_RSRC(a.vpos + vw.w0, wlive);
+    const auto d_cig = PHZ_STAGE_RSRC(a.cigar + cw.c_begin, cnt_w);
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+        const int j = k * MAP_BLOCK + tid;
+        rpos_[k] = (int)PHZ_STAGE_WORD(d_pos, j);
+        soff_[k] = PHZ_STAGE_WORD(d_soff, j);
+        coff_[k] = PHZ_STAGE_WORD(d_coff, stage_coff_index(j, nr));      // a lane past the tile keeps cigar_off[r0 + nr]: phase 1a reads s_coff[j + 1]
+    }
+    // cigar_off[r0 + nr] without a load: the pre-pass stored cigar_off[first] and cigar_off[last + 1] - cigar_off[first] of the SAME records (k_tile_window
+    // is launched with tile_reads == TILE: launch_k_map asserts it on the host), and their sum is that word
+    const uint32_t coff_end = (uint32_t)tw.z + (uint32_t)tw.w;
+    const uint32_t v_raw = PHZ_STAGE_WORD(d_win, tid);
+#pragma unroll
+    for (int u = 0; u < 3; u++) cg[u] = PHZ_STAGE_WORD(d_cig, (uint32_t)tid + (uint32_t)u * MAP_BLOCK);
+    const int v_first = (uint32_t)tid < wlive ? (int)v_raw : 0x7fffffff;
+#else
 #pragma unroll
     for (int k = 0; k < RPT; k++) {
         const int j = k * MAP_BLOCK + tid;
@@ -605,9 +630,9 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     const uint32_t coff_end = a.cigar_off[r0 + nr];
     int v_first = 0x7fffffff;
     if (tid < vw.wlen) { const int idx = vw.w0 + tid; v_first = idx < a.nv ? a.vpos[idx] : 0x7fffffff; }
-    uint32_t cg[3] = {0, 0, 0};
 #pragma unroll
     for (int u = 0; u < 3; u++) { const uint32_t j = (uint32_t)tid + (uint32_t)u * MAP_BLOCK; if (j < cnt_w) cg[u] = a.cigar[cw.c_begin + j]; }
+#endif
 #pragma unroll
     for (int k = 0; k < RPT; k++) {
         const int j = k * MAP_BLOCK + tid;
@@ -624,6 +649,17 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
     const int wfill = (1 << wdepth) > vw.wlen ? (1 << wdepth) : vw.wlen;
 #endif
     if (tid < wfill) s_vpos[tid] = v_first;
+#ifndef PHZ_MAP_FLAT_STAGE
+    for (int j = tid + MAP_BLOCK; j < wfill; j += MAP_BLOCK) {
+        const uint32_t v = PHZ_STAGE_WORD(d_win, j);
+        s_vpos[j] = (uint32_t)j < wlive ? (int)v : 0x7fffffff;
+    }
+    // the three unrolled rounds store without a test: 3 * MAP_BLOCK words are inside s_cig, and a word past cnt_w (loaded as 0) is read by nobody
+    static_assert(3 * MAP_BLOCK <= CIG, "the unrolled CIGAR rounds stay inside s_cig");
+#pragma unroll
+    for (int u = 0; u < 3; u++) s_cig[(uint32_t)tid + (uint32_t)u * MAP_BLOCK] = cg[u];
+    for (uint32_t j = (uint32_t)tid + 3u * MAP_BLOCK; j < cnt_w; j += MAP_BLOCK) s_cig[j] = PHZ_STAGE_WORD(d_cig, j);
+#else
     for (int j = tid + MAP_BLOCK; j < wfill; j += MAP_BLOCK) {
         const int idx = vw.w0 + j;
         s_vpos[j] = (j < vw.wlen && idx < a.nv) ? a.vpos[idx] : 0x7fffffff;
@@ -631,6 +667,7 @@ __device__ __forceinline__ void map_tile(const MapBatch &bt, const int64_t gtile
 #pragma unroll
     for (int u = 0; u < 3; u++) { const uint32_t j = (uint32_t)tid + (uint32_t)u * MAP_BLOCK; if (j < cnt_w) s_cig[j] = cg[u]; }
     for (uint32_t j = (uint32_t)tid + 3u * MAP_BLOCK; j < cnt_w; j += MAP_BLOCK) s_cig[j] = a.cigar[cw.c_begin + j];
+#endif
     __syncthreads();
     PHZ_STAMP(1);
     CandBuf cb;
@@ -1312,6 +1349,9 @@ struct MapSubmission {
     }
     template <int B, int R> void launch_k_map(const MapBatch &bt) const {
         const dim3 grid((unsigned)ntiles), block(B);
+        // k_map takes cigar_off[last + 1] of a tile from the pre-pass's words: both must cut the shard into the same tiles.  A host check, one integer compare
+        // per launch; the library's build (_lib.build) does not define NDEBUG, so it is compiled in -- a build with -DNDEBUG drops it
+        assert(tile_reads == B * R);
         if constexpr (B * R <= STAGE4_MAX_TILE_READS) {
             if (narrow) {
                 if (one_plane) hipLaunchKernelGGL((k_map<B, R, false, true, true>), grid, block, knobs.dyn_lds, sm, bt);
