@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_CISSCAN = 16, PHZ_T_COUNT = 17 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_CISSCAN = 16, PHZ_T_FISHER = 17, PHZ_T_CMH = 18, PHZ_T_COUNT = 19 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -854,6 +854,38 @@ int phz_betabinom_fit(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_
                       double *loglik_out, int64_t *n_used_out, int space);
 int phz_betabinom_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a, const int32_t *b, double p0, const double *rho, int32_t min_cov,
                        double *pvalue, int space);
+
+/* ---- phaser_ae_diff (phaser_amd/ae_diff.py; no counterpart in the reference): allelic imbalance compared between two conditions of the same individuals ---
+ * a1, b1 and a2, b2: the aCount and bCount matrices of condition 1 and of condition 2, row-major n_rows x n_cols [genes, samples], at most 2^31 - 1 cells; cell
+ * (r, c) is the 2 x 2 table [[a1, b1], [a2, b2]].  n1 = a1 + b1, n2 = a2 + b2, m = a1 + a2, N = n1 + n2.  A cell is tested when all four counts are >= 0 and
+ * n1 and n2 are both >= the larger of min_cov and 1.  N must fit in int32: checked for PHZ_HOST inputs (PHZ_E_ARG), the caller's guarantee with PHZ_DEVICE.
+ * All in fp64.  PHZ_E_ARG (more than 2^31 - 1 cells, an N beyond int32) sets the phz_last_error text and leaves the outputs untouched.
+ *
+ * phz_fisher_test (K_fisher): the two-sided Fisher exact test of R's fisher.test per cell.  Over the support x in [max(0, m - n2), min(n1, m)] of
+ * pmf(x) = C(n1, x) C(n2, m - x) / C(N, m), with k = a1: pvalue = min(1, the sum of pmf(i) over ALL i of the support with pmf(i) <= pmf(k) (1 + 1e-7)); NaN where
+ * the cell is not tested.  The pmf is unimodal: the near tail runs outward from k, the far tail outward from an index found by bisection of log pmf (through
+ * lgamma) on the other side of the mode; each is summed by the recurrence pmf(x+1) / pmf(x) = (n1 - x)(m - x) / ((x + 1)(n2 - m + x + 1)) until a term falls
+ * below 1e-18 of the running sum.  A pmf(k) that underflows gives 0; a one-point support (m = 0 or m = N) gives 1.  Where n1 == n2 or 2 m == N the pmf is
+ * symmetric and the far index is the exact mirror of k, without a search.  Elsewhere an exact tie pmf(i) == pmf(k) across the mode is told from lgamma's
+ * rounding by the relative 1e-7 alone, which holds up to N of about 6 * 10^6 (the error of a log pmf, about 2^-50 (N + 1) ln(N + 2), reaches 1e-7 there).
+ * Cells with N above PHZ_FISHER_WAVE_N are taken one wave per cell, the others one lane per cell (by default every cell: the threshold is 2^31 - 1); within
+ * a tier the bits depend on the inputs alone, not on the memory space or the run.  Timed into PHZ_T_FISHER.
+ *
+ * phz_cmh_test (K_cmh): the Cochran-Mantel-Haenszel test of R's mantelhaen.test per row, the columns as strata.  A stratum is a tested cell with N >= 2.
+ * Over a row's strata D = sum of (a1 - n1 m / N), V = sum of n1 n2 m (N - m) / (N^2 (N - 1)), R = sum of a1 b2 / N, S = sum of b1 a2 / N; then
+ *   n_strata[r] = the number of strata
+ *   stat[r]     = (|D| - Y)^2 / V with Y = 0.5 when correct != 0 and |D| >= 0.5, else 0
+ *   pvalue[r]   = erfc(sqrt(stat / 2)), the upper tail of chi-square with one degree of freedom
+ *   log2_or[r]  = log2(R / S), the Mantel-Haenszel common odds ratio; S = 0 < R: +inf, R = 0 < S: -inf, both 0: NaN
+ * stat and pvalue are NaN when n_strata < the larger of min_samples and 1, or V == 0.  One wave per row; every sum is taken per lane in column order and
+ * combined by a fixed butterfly, so the bits depend on the inputs alone.  Timed into PHZ_T_CMH. */
+#ifndef PHZ_FISHER_WAVE_N
+#define PHZ_FISHER_WAVE_N 2147483647          /* no cell lies above it: the wave tier is off by default (it did not pay in the A/B); -D overrides */
+#endif
+int phz_fisher_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a1, const int32_t *b1, const int32_t *a2, const int32_t *b2, int32_t min_cov,
+                    double *pvalue, int space);
+int phz_cmh_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a1, const int32_t *b1, const int32_t *a2, const int32_t *b2, int32_t min_cov,
+                 int32_t min_samples, int32_t correct, double *stat, double *pvalue, double *log2_or, int32_t *n_strata, int space);
 
 /* K_blnfit and K_blntest (phaser_amd/ae_outlier.py): per gene, how much the allelic ratio varies in the population, and which samples are outliers against
  * that.  With null ratio p0 and mu0 = logit(p0):

@@ -21,9 +21,11 @@ PHZ_OK, PHZ_E_ARG, PHZ_E_HIP, PHZ_E_CAPACITY, PHZ_E_UNSUPPORTED, PHZ_E_NOMEM = 0
 PHZ_HOST, PHZ_DEVICE = 0, 1
 PHZ_T_MAP, PHZ_T_ASHIST, PHZ_T_TALLY, PHZ_T_COMPONENTS, PHZ_T_GENES, PHZ_T_INFLATE, PHZ_T_BAMPACK, PHZ_T_ROWS, PHZ_T_BOOT, PHZ_T_ANNOT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 PHZ_T_BINOM, PHZ_T_BH, PHZ_T_BBFIT, PHZ_T_BBTEST, PHZ_T_BLNFIT, PHZ_T_BLNTEST, PHZ_T_CISSCAN = 10, 11, 12, 13, 14, 15, 16
-PHZ_T_COUNT = 17
+PHZ_T_FISHER, PHZ_T_CMH = 17, 18
+PHZ_T_COUNT = 19
 PHZ_CISSCAN_MAX_S = 4096
 PHZ_BB_RHO_MIN, PHZ_BB_FIT_CANDIDATES, PHZ_BB_FIT_ROUNDS = 1e-6, 64, 4
+PHZ_FISHER_WAVE_N = 2 ** 31 - 1          # the header's default: K_fisher takes cells with N above it one wave per cell, so none
 PHZ_BLN_S_MIN, PHZ_BLN_S_MAX, PHZ_BLN_FIT_CANDIDATES, PHZ_BLN_FIT_ROUNDS = 1e-3, 2.0, 64, 4
 PHZ_ANNOT_BOTH, PHZ_ANNOT_FIRST = 1, 2
 PHZ_ANNOT_BATCH_ROWS = 1 << 24
@@ -366,6 +368,9 @@ SYMBOLS = {
     "phz_betabinom_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
     "phz_bln_fit": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_bln_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
+    "phz_fisher_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
+    "phz_cmh_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_int]),
     "phz_cis_scan": (C.c_int, [C.c_void_p, C.POINTER(phz_cisscan_in), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_vcf_region_classes": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),

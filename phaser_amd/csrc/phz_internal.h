@@ -53,6 +53,8 @@ enum PhzScratch {
     SC_BB_COLPAR = 3, SC_BB_FLAG = 4, SC_BB_POS = 5, SC_BB_LIST = 6, SC_BB_SCAN_TMP = 7,
     // K_blntest (phz_bln_test): 1 / s per row, NaN where the row is not tested (K_blnfit keeps everything in registers)
     SC_BLN_ROWPAR = 0,
+    // K_fisher (phz_fisher_test): wave-tier flag of every cell, its exclusive scan, the listed cells, the scan's temporary (K_cmh keeps everything in registers)
+    SC_FISHER_FLAG = 0, SC_FISHER_POS = 1, SC_FISHER_LIST = 2, SC_FISHER_SCAN_TMP = 3,
     SC_COUNT = 24
 };
 
