@@ -181,7 +181,7 @@ typedef struct {
 } phz_variants_general;
 
 /* timing slots for phz_get_timing */
-enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_CISSCAN = 16, PHZ_T_FISHER = 17, PHZ_T_CMH = 18, PHZ_T_COUNT = 19 };
+enum { PHZ_T_MAP = 0, PHZ_T_ASHIST = 1, PHZ_T_TALLY = 2, PHZ_T_COMPONENTS = 3, PHZ_T_GENES = 4, PHZ_T_INFLATE = 5, PHZ_T_BAMPACK = 6, PHZ_T_ROWS = 7, PHZ_T_BOOT = 8, PHZ_T_ANNOT = 9, PHZ_T_BINOM = 10, PHZ_T_BH = 11, PHZ_T_BBFIT = 12, PHZ_T_BBTEST = 13, PHZ_T_BLNFIT = 14, PHZ_T_BLNTEST = 15, PHZ_T_CISSCAN = 16, PHZ_T_FISHER = 17, PHZ_T_CMH = 18, PHZ_T_MATCH = 19, PHZ_T_COUNT = 20 };
 
 /* work counters accumulated over phz_tally calls since the last phz_reset_timing (the units of K_tally's byte model):
  * call lines seen, distinct (QNAME, variant, class) items, pair events = sum over QNAMEs of C(k, 2) item pairs on different
@@ -462,6 +462,16 @@ int phz_tabix_lines(const char *path, int64_t n_keys, const char *const *contig,
  * the alternative allele of a het is on haplotype 2 (GT 0|1).  *contigs_out as phz_vcf_lookup.  Both buffers are released with phz_buf_free. */
 int phz_vcf_region_classes(const char *path, int64_t n_regions, const char *const *contig, const int64_t *lo, const int64_t *hi, int32_t n_samples,
                            const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
+
+/* phaser_amd.sample_match's reader: the records of a bgzipped VCF at n_keys (contig, 1-based pos) keys, with the key handling, index chunks, whole-file scan
+ * and threads of phz_vcf_lookup, reduced to one genotype code per named sample.  *out: one line per record at a key, in file order,
+ * "key\tCHROM\tPOS\tID\tREF\tALT\tgi\tcodes\n", gi = the index of GT in FORMAT (-1: none) and codes = one character '0' + code per sample.  The GT subfield is
+ * split on '/' or '|' (phasing does not matter): both alleles "0" give code 1 (hom-ref), one "0" and one "1" in either order 2 (het), both "1" 3 (hom-alt);
+ * everything else gives 0: ".", "./.", a haploid call, an allele of 2 or more, a sample the header or the record lacks, no GT in FORMAT.  REF and ALT are
+ * reported as written: telling a multi-allelic record from the caller's allele pair is the caller's.  *contigs_out as phz_vcf_lookup.  Both buffers are
+ * released with phz_buf_free. */
+int phz_vcf_site_genotypes(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples, const char *const *samples,
+                           int use_index, int threads, char **out, int64_t *out_len, char **contigs_out, int64_t *contigs_len);
 
 /* whole BGZF file -> buffer owned by the library (release it with phz_buf_free and nothing else: a large text is an anonymous mapping, not a malloc'd block);
  * PHZ_E_UNSUPPORTED when the file is plain gzip */
@@ -886,6 +896,35 @@ int phz_fisher_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t 
                     double *pvalue, int space);
 int phz_cmh_test(phz_ctx *ctx, int64_t n_rows, int64_t n_cols, const int32_t *a1, const int32_t *b1, const int32_t *a2, const int32_t *b2, int32_t min_cov,
                  int32_t min_samples, int32_t correct, double *stat, double *pvalue, double *log2_or, int32_t *n_strata, int space);
+
+/* ---- phaser_sample_match (phaser_amd/sample_match.py; no counterpart in the reference): which donor of a population VCF a sample's reads came from ---
+ * K_match.  geno[n_sites * n_donors], row-major: the genotype code of (site, donor), 0 no call, 1 hom-ref, 2 het, 3 hom-alt (phz_vcf_site_genotypes' codes;
+ * the two low bits are read).  Sample s owns the entries [e_off[s], e_off[s + 1]): a site (a row of geno) with the sample's reference and alternative read
+ * counts.  log_ref[g - 1] and log_alt[g - 1]: log P(a read shows ref) and log P(a read shows alt) under genotype code g; the library takes no logarithm.
+ *
+ * Every symbol below is determined by the inputs alone.  Per entry:
+ *   total = ref + alt, in int64.  cap > 0 and total > cap: r = (ref cap + total / 2) / total in int64 with floor division, a = cap - r; otherwise r = ref, a = alt.
+ *   t_g = fma((double)r, log_ref[g - 1], (double)a * log_alt[g - 1]) for g = 1, 2, 3: one rounded product and one fused multiply-add.
+ *   obs, from the raw counts with m = min(ref, alt): 2 when 1000 m >= het_permille total (int64); otherwise 1 when ref > alt, else 3.
+ * Per (sample s, donor d), over the entries of s in entry order with g = the donor's code at the entry's site: g = 0 adds nothing; otherwise
+ *   loglik[s * n_donors + d] += t_g (one fp64 add per entry, sequentially, starting from +0.0), n_called += 1, n_match += (g == obs).
+ * There is no tree, no atomic and no dependence on the grid, on PHZ_HOST / PHZ_DEVICE or on the run: a donor's result does not depend on which other donors
+ * or samples are in the call.  Outputs are row-major [n_samples * n_donors].
+ *
+ * A bad entry has site < 0, site >= n_sites, a negative count or total == 0.  With PHZ_HOST inputs it is PHZ_E_ARG, as is an e_off that does not ascend from
+ * 0; with PHZ_DEVICE a bad entry is skipped, nothing is read out of bounds, and e_off is the caller's guarantee.  n_donors < 1, het_permille outside
+ * [1, 500] and cap < 0 are PHZ_E_ARG in either space.  PHZ_E_ARG leaves the outputs untouched.  Zero samples, zero sites or zero entries is a valid call.
+ * The packing of the codes into 2 bits per donor and the sums are timed together into PHZ_T_MATCH. */
+typedef struct {
+    int64_t n_sites, n_samples;
+    int32_t n_donors;
+    const uint8_t *geno;                                    /* [n_sites * n_donors] */
+    const int64_t *e_off;                                   /* [n_samples + 1] */
+    const int32_t *e_site, *e_ref, *e_alt;                  /* [e_off[n_samples]] */
+    double log_ref[3], log_alt[3];                          /* per genotype code 1, 2, 3 */
+    int32_t cap, het_permille;
+} phz_match_in;
+int phz_sample_match(phz_ctx *ctx, const phz_match_in *in, double *loglik, int32_t *n_called, int32_t *n_match, int space);
 
 /* K_blnfit and K_blntest (phaser_amd/ae_outlier.py): per gene, how much the allelic ratio varies in the population, and which samples are outliers against
  * that.  With null ratio p0 and mu0 = logit(p0):

@@ -21,8 +21,8 @@ PHZ_OK, PHZ_E_ARG, PHZ_E_HIP, PHZ_E_CAPACITY, PHZ_E_UNSUPPORTED, PHZ_E_NOMEM = 0
 PHZ_HOST, PHZ_DEVICE = 0, 1
 PHZ_T_MAP, PHZ_T_ASHIST, PHZ_T_TALLY, PHZ_T_COMPONENTS, PHZ_T_GENES, PHZ_T_INFLATE, PHZ_T_BAMPACK, PHZ_T_ROWS, PHZ_T_BOOT, PHZ_T_ANNOT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 PHZ_T_BINOM, PHZ_T_BH, PHZ_T_BBFIT, PHZ_T_BBTEST, PHZ_T_BLNFIT, PHZ_T_BLNTEST, PHZ_T_CISSCAN = 10, 11, 12, 13, 14, 15, 16
-PHZ_T_FISHER, PHZ_T_CMH = 17, 18
-PHZ_T_COUNT = 19
+PHZ_T_FISHER, PHZ_T_CMH, PHZ_T_MATCH = 17, 18, 19
+PHZ_T_COUNT = 20
 PHZ_CISSCAN_MAX_S = 4096
 PHZ_BB_RHO_MIN, PHZ_BB_FIT_CANDIDATES, PHZ_BB_FIT_ROUNDS = 1e-6, 64, 4
 PHZ_FISHER_WAVE_N = 2 ** 31 - 1          # the header's default: K_fisher takes cells with N above it one wave per cell, so none
@@ -180,6 +180,11 @@ class phz_cisscan_in(C.Structure):
     _fields_ = [("n_genes", C.c_int64), ("n_vars", C.c_int64), ("n_samples", C.c_int32), ("cls", C.c_void_p), ("g_off", C.c_void_p), ("covered", C.c_void_p),
                 ("order", C.c_void_p), ("run_first", C.c_void_p), ("run_last", C.c_void_p), ("v_lo", C.c_void_p), ("v_hi", C.c_void_p), ("subseq", C.c_void_p),
                 ("min_het", C.c_int32), ("min_hom", C.c_int32), ("n_perm", C.c_int32), ("seed", C.c_uint64)]
+
+
+class phz_match_in(C.Structure):
+    _fields_ = [("n_sites", C.c_int64), ("n_samples", C.c_int64), ("n_donors", C.c_int32), ("geno", C.c_void_p), ("e_off", C.c_void_p), ("e_site", C.c_void_p),
+                ("e_ref", C.c_void_p), ("e_alt", C.c_void_p), ("log_ref", C.c_double * 3), ("log_alt", C.c_double * 3), ("cap", C.c_int32), ("het_permille", C.c_int32)]
 
 
 class phz_annot_in(C.Structure):
@@ -371,8 +376,11 @@ SYMBOLS = {
     "phz_fisher_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int]),
     "phz_cmh_test": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_int]),
+    "phz_sample_match": (C.c_int, [C.c_void_p, C.POINTER(phz_match_in), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_cis_scan": (C.c_int, [C.c_void_p, C.POINTER(phz_cisscan_in), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "phz_vcf_region_classes": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int, C.c_int,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "phz_vcf_site_genotypes": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int, C.c_int,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "phz_aematrix_parse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),

@@ -55,6 +55,8 @@ enum PhzScratch {
     SC_BLN_ROWPAR = 0,
     // K_fisher (phz_fisher_test): wave-tier flag of every cell, its exclusive scan, the listed cells, the scan's temporary (K_cmh keeps everything in registers)
     SC_FISHER_FLAG = 0, SC_FISHER_POS = 1, SC_FISHER_LIST = 2, SC_FISHER_SCAN_TMP = 3,
+    // K_match (phz_sample_match): the genotype codes packed 2 bits per donor (the sums stay in registers)
+    SC_MATCH_WORDS = 0,
     SC_COUNT = 24
 };
 

@@ -12,6 +12,8 @@
 // phz_vcf_region_classes (phaser_cis_scan) asks by region instead of by position: the regions of a contig are merged into disjoint intervals, the index path
 // collects the chunks of every interval's bins, and a matching line is reduced to its five leading fields, the GT index and one class character per sample
 // (class_code: cis_var's _classify).  A record inside several of the caller's regions is reported once, since the lines are scanned once, in file order.
+//
+// phz_vcf_site_genotypes (phaser_sample_match) is phz_vcf_lookup with the GT texts reduced to one genotype code per sample (geno_code).
 #include <fcntl.h>
 #include <limits.h>
 #include <stdint.h>
@@ -46,6 +48,7 @@ struct Ctx {
     // phz_vcf_region_classes: records inside a region instead of records at a key; per contig the merged [lo, hi] intervals (1-based, inclusive), ascending
     const int64_t *hi = nullptr;
     std::unordered_map<std::string, std::vector<std::pair<int64_t, int64_t>>> regions;
+    bool geno = false;                     // phz_vcf_site_genotypes: records at a key, one genotype code per sample instead of the GT texts
 };
 
 // phaser_amd.cis_var's _classify and its phased test on one GT text -> '0' + class (+ 4: the "1" of a het is the second field)
@@ -62,6 +65,26 @@ char class_code(std::string_view gt) {
         }
     }
     return (zeros == 2 || ones == 2) ? '2' : '0';
+}
+
+// phaser_amd.sample_match's genotype of one GT text -> '0' + code: two alleles split by '/' or '|'; "0" and "0": 1, one "0" and one "1": 2, "1" and "1": 3;
+// everything else (".", "./.", one allele, three, an allele of 2 or more): 0
+char geno_code(std::string_view gt) {
+    const size_t sep = gt.find_first_of("/|");
+    if (sep == std::string_view::npos) return '0';
+    const std::string_view x = gt.substr(0, sep), y = gt.substr(sep + 1);
+    if ((x != "0" && x != "1") || (y != "0" && y != "1")) return '0';
+    return (char)('1' + (x == "1") + (y == "1"));
+}
+
+// the GT subfield (index gi of FORMAT) of sample column text v; false: the column has fewer subfields
+bool gt_subfield(std::string_view v, int gi, std::string_view *gt) {
+    size_t a = 0; int idx = 0;
+    while (idx < gi && a != std::string_view::npos) { a = v.find(':', a); if (a != std::string_view::npos) a++; idx++; }
+    if (a == std::string_view::npos) return false;
+    const size_t b = v.find(':', a);
+    *gt = v.substr(a, b == std::string_view::npos ? std::string_view::npos : b - a);
+    return true;
 }
 
 // one record line -> output line "key\tCHROM\tPOS\tID\tREF\tALT\tgi\tGT...\n" (GT of a column the line lacks: "\x01")
@@ -97,8 +120,13 @@ void emit(const Ctx &C, int64_t key, std::string_view line, std::string &out) {
         }
     }
     out += '\t'; out += std::to_string(gi);
-    if (C.hi) out += '\t';
+    if (C.hi || C.geno) out += '\t';
     for (int32_t c : C.scol) {
+        if (C.geno) {                                                // one genotype character per sample
+            std::string_view gt;
+            out += gi >= 0 && c >= 0 && (size_t)c < f.size() && gt_subfield(f[(size_t)c], gi, &gt) ? geno_code(gt) : '0';
+            continue;
+        }
         if (C.hi) {                                                  // one class character per sample
             char code = '0';
             if (gi >= 0 && c >= 0 && (size_t)c < f.size()) {
@@ -401,6 +429,15 @@ extern "C" int phz_vcf_lookup(const char *path, int64_t n_keys, const char *cons
                               int64_t *contigs_len) {
     if (n_samples < 0 || (n_samples && !samples)) return PHZ_E_ARG;
     Ctx C;
+    return lookup(C, path, n_keys, contig, pos, n_samples, samples, use_index, threads, out, out_len, contigs_out, contigs_len);
+}
+
+extern "C" int phz_vcf_site_genotypes(const char *path, int64_t n_keys, const char *const *contig, const int64_t *pos, int32_t n_samples,
+                                      const char *const *samples, int use_index, int threads, char **out, int64_t *out_len, char **contigs_out,
+                                      int64_t *contigs_len) {
+    if (n_samples < 0 || (n_samples && !samples)) return PHZ_E_ARG;
+    Ctx C;
+    C.geno = true;
     return lookup(C, path, n_keys, contig, pos, n_samples, samples, use_index, threads, out, out_len, contigs_out, contigs_len);
 }
 
