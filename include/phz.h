@@ -742,7 +742,18 @@ void phz_hc_free(phz_hc *h);
 
 /* K_genes: distinct reads per haplotype for every (row, feature) pair (variant_feature_reads :172-219).  A work item is a
  * slice of one row-haplotype label run: labels [item_lo, item_lo + item_n), run start item_run (lab_prev is run-relative).
- * pair_counts[2*pair + hap] receives the count; pair_begin / pair_end are the feature's BED start / stop. */
+ * pair_counts[2*pair + hap] receives the count; pair_begin / pair_end are the feature's BED start / stop.  A variant at position pos
+ * lies inside when pair_begin <= pos - 1 <= pair_end (the end is inclusive, :194); a pair with pair_begin > pair_end counts 0.  The items
+ * of one (pair, hap) together cover the labels of one run once, in any order and cut anywhere (item_n == 0 is allowed); a pair without
+ * items reads 0.  Exactly 2 * n_pairs cells are written.  n_pairs == 0 with n_items == 0 is PHZ_OK and touches nothing (pair_counts may
+ * be NULL); n_pairs == 0 with items is PHZ_E_ARG, as are a negative count and a NULL array whose count is not 0.
+ * PHZ_HOST arrays are checked before anything is staged or launched (one pass over the items and over lab_prev of the labels they cover,
+ * on up to 8 host threads from 2^20 labels on; PHZ_E_ARG with a phz_last_error text, nothing written):
+ *   item_n >= 0; item_hap 0 or 1; 0 <= item_pair < n_pairs; 0 <= item_run <= item_lo; item_lo + item_n <= n_lab of that haplotype;
+ *   -1 <= lab_prev[p] < p - item_run for every label p of the item, so a chain only moves backwards inside its run and ends.
+ * One limit: a chain may step onto a label of the run that no item covers, and that label's lab_prev is not checked (the read stays
+ * inside the array, the chain's end is not guaranteed); phaser_amd/gene_ae.py always covers whole runs.
+ * With PHZ_DEVICE nothing on the device is read by the host: all of the above is the caller's guarantee. */
 typedef struct {
     int64_t n_items;
     const int64_t *item_lo;

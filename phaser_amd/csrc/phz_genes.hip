@@ -9,7 +9,13 @@
 // row's variants, in any order.  HBM-bound: 8 B per label visited (+ the chain), no reuse -> plain coalesced streaming,
 // one work item = (pair, haplotype, <= ITEM_LABELS labels) per wave so that a block with millions of labels spreads
 // over the chip; per-item partial counts are added to the pair's counter.
+// Tested directly by tests/test_gene_counts.py (designed inputs of tests/gene_counts_inputs.py against a set union over the label lists;
+// emulation and GPU, PHZ_HOST and PHZ_DEVICE, argument checks and refusals).
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <thread>
+#include <vector>
 
 #include "phz.h"
 #include "phz_internal.h"
@@ -48,11 +54,69 @@ __global__ __launch_bounds__(256) void k_gene_items(int64_t n_items, const int64
     if (lane == 0 && cnt) atomicAdd(&counts[2 * (int64_t)pair + hap], cnt);
 }
 
+// What PHZ_HOST callers hand over is checked before the first HIP call (include/phz.h states the rules): every index the kernel
+// follows stays inside the arrays, and a prev chain only moves backwards inside its run, so it ends.  One pass over the items
+// and over lab_prev of the labels they cover; from CHECK_THREADS_MIN_LABELS labels on, the items are shared out among up to
+// CHECK_THREADS host threads (the pass reads 4 B per label next to a copy of 8 B per label).
+constexpr int CHECK_THREADS = 8;
+constexpr int64_t CHECK_THREADS_MIN_LABELS = 1 << 20;
+
+// first broken rule among the items [i0, i1), nullptr if none
+const char *check_items(const phz_gene_work *w, int64_t i0, int64_t i1) {
+    for (int64_t it = i0; it < i1; it++) {
+        const int64_t lo = w->item_lo[it], run = w->item_run[it], n = w->item_n[it];
+        const int hap = w->item_hap[it];
+        if (n < 0) return "phz_gene_counts: negative item_n";
+        if (hap > 1) return "phz_gene_counts: item_hap is neither 0 nor 1";
+        if (w->item_pair[it] < 0 || w->item_pair[it] >= w->n_pairs) return "phz_gene_counts: item_pair outside [0, n_pairs)";
+        const int64_t n_lab = hap ? w->n_lab_b : w->n_lab_a;
+        if (run < 0 || run > lo || lo > n_lab || n > n_lab - lo) return "phz_gene_counts: item outside its label array (0 <= item_run <= item_lo, item_lo + item_n <= n_lab)";
+        const int32_t *prev = (hap ? w->lab_prev_b : w->lab_prev_a) + lo;
+        const int64_t rel = lo - run;                    // run-relative index of the item's first label
+        unsigned bad = 0;
+        if (rel + n <= INT32_MAX) {                      // -1 <= prev < rel + i  <=>  (unsigned)(prev + 1) <= rel + i, which the compiler vectorizes
+            const uint32_t r = (uint32_t)rel;
+            for (uint32_t i = 0; i < (uint32_t)n; i++) bad |= ((uint32_t)prev[i] + 1u) > (r + i);
+        } else {
+            for (int64_t i = 0; i < n; i++) bad |= (prev[i] < -1) | (prev[i] >= rel + i);
+        }
+        if (bad) return "phz_gene_counts: lab_prev does not point backwards inside its run (-1 <= lab_prev[p] < p - item_run)";
+    }
+    return nullptr;
+}
+
+int check_gene_work(phz_ctx *ctx, const phz_gene_work *w) {
+    int nt = 1;
+    if (w->n_lab_a + w->n_lab_b >= CHECK_THREADS_MIN_LABELS)
+        nt = (int)std::min<int64_t>(std::min<int64_t>(CHECK_THREADS, std::max(1u, std::thread::hardware_concurrency())), std::max<int64_t>(1, w->n_items));
+    std::vector<const char *> msg((size_t)nt, nullptr);
+    if (nt == 1) msg[0] = check_items(w, 0, w->n_items);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; t++) th.emplace_back([&, t]() { msg[(size_t)t] = check_items(w, w->n_items * t / nt, w->n_items * (t + 1) / nt); });
+        for (auto &t : th) t.join();
+    }
+    for (const char *m : msg) if (m) return phz_fail(ctx, PHZ_E_ARG, m);       // the lowest item's
+    return PHZ_OK;
+}
+
 }  // namespace
 
 extern "C" int phz_gene_counts(phz_ctx *ctx, const phz_gene_work *w, int32_t *pair_counts, int space) {
     PhzEnter phz_guard_(ctx);
-    if (!ctx || !w || (!pair_counts && w->n_pairs) || w->n_items < 0 || w->n_pairs < 0) return PHZ_E_ARG;
+    if (!ctx) return PHZ_E_ARG;
+    if (!w) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: work is NULL");
+    if (space != PHZ_HOST && space != PHZ_DEVICE) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: bad memory space");
+    if (w->n_items < 0 || w->n_pairs < 0 || w->n_lab_a < 0 || w->n_lab_b < 0) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: negative count");
+    if (w->n_items >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "too many gene work items");
+    if (w->n_pairs == 0) {                                // nothing to count and nothing to clear: pair_counts holds no cell
+        if (w->n_items) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: items without pairs (an item must name a pair)");
+        return PHZ_OK;
+    }
+    if (!pair_counts || !w->pair_begin || !w->pair_end) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: NULL pair array");
+    if (w->n_items && (!w->item_lo || !w->item_n || !w->item_run || !w->item_pair || !w->item_hap)) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: NULL item array");
+    if ((w->n_lab_a && (!w->lab_pos_a || !w->lab_prev_a)) || (w->n_lab_b && (!w->lab_pos_b || !w->lab_prev_b))) return phz_fail(ctx, PHZ_E_ARG, "phz_gene_counts: NULL label array");
+    if (space == PHZ_HOST) if (int s = check_gene_work(ctx, w)) return s;
     PHZ_HIP(ctx, hipSetDevice(ctx->device));
     Staging st(ctx);
     const int64_t *d_lo, *d_run; const int32_t *d_n, *d_pair, *d_pb, *d_pe, *d_posa, *d_preva, *d_posb, *d_prevb; const uint8_t *d_hap;
@@ -71,9 +135,8 @@ extern "C" int phz_gene_counts(phz_ctx *ctx, const phz_gene_work *w, int32_t *pa
     if (int s = st.out(pair_counts, (size_t)w->n_pairs * 2, space, &d_counts)) return s;
     hipStream_t sm = ctx->stream;
     (void)hipEventRecord(ctx->ev0, sm);
-    PHZ_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t)(w->n_pairs ? w->n_pairs : 1) * 8, sm));
+    PHZ_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t)w->n_pairs * 8, sm));
     if (w->n_items > 0) {
-        if (w->n_items >= (1ll << 31)) return phz_fail(ctx, PHZ_E_ARG, "too many gene work items");
         hipLaunchKernelGGL(k_gene_items, dim3((unsigned)((w->n_items + 3) / 4)), dim3(256), 0, sm, w->n_items, d_lo, d_n, d_run, d_pair, d_hap, d_pb, d_pe,
                            d_posa, d_preva, d_posb, d_prevb, d_counts);
         PHZ_HIP(ctx, hipGetLastError());
@@ -82,7 +145,7 @@ extern "C" int phz_gene_counts(phz_ctx *ctx, const phz_gene_work *w, int32_t *pa
     (void)hipEventSynchronize(ctx->ev1);
     float ms = 0; (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     ctx->last_ms[PHZ_T_GENES] = ms; ctx->total_ms[PHZ_T_GENES] += ms; ctx->launches[PHZ_T_GENES]++;
-    if (space == PHZ_HOST && w->n_pairs) PHZ_HIP(ctx, hipMemcpyAsync(pair_counts, d_counts, (size_t)w->n_pairs * 8, hipMemcpyDeviceToHost, sm));
+    if (space == PHZ_HOST) PHZ_HIP(ctx, hipMemcpyAsync(pair_counts, d_counts, (size_t)w->n_pairs * 8, hipMemcpyDeviceToHost, sm));
     PHZ_HIP(ctx, hipStreamSynchronize(sm));
     return PHZ_OK;
 }

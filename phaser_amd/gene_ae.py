@@ -90,6 +90,23 @@ def _expand(counts):
     return owner, np.arange(total, dtype=np.int64) - np.repeat(first, counts)
 
 
+def work_items(lab_off, rows, pairs):
+    """K_genes work items of pairs[k] = (row rows[k], some feature): both haplotypes' whole label runs of the row, cut into slices of
+    ITEM_LABELS labels -> item_lo, item_n, item_run, item_pair, item_hap of a phz_gene_work"""
+    items = {"lo": [], "n": [], "run": [], "pair": [], "hap": []}
+    for hap in (0, 1):
+        run0 = lab_off[hap][rows]; ln = lab_off[hap][rows + 1] - run0
+        nch = (ln + ITEM_LABELS - 1) // ITEM_LABELS
+        owner2, j = _expand(nch)
+        lo2 = run0[owner2] + j * ITEM_LABELS
+        items["lo"].append(lo2); items["n"].append(np.minimum(ITEM_LABELS, run0[owner2] + ln[owner2] - lo2))
+        items["run"].append(run0[owner2]); items["pair"].append(pairs[owner2]); items["hap"].append(np.full(len(owner2), hap, dtype=np.uint8))
+    it_lo = np.ascontiguousarray(np.concatenate(items["lo"]), dtype=np.int64); it_n = np.ascontiguousarray(np.concatenate(items["n"]), dtype=np.int32)
+    it_run = np.ascontiguousarray(np.concatenate(items["run"]), dtype=np.int64)
+    it_pair = np.ascontiguousarray(np.concatenate(items["pair"]), dtype=np.int32); it_hap = np.ascontiguousarray(np.concatenate(items["hap"]), dtype=np.uint8)
+    return it_lo, it_n, it_run, it_pair, it_hap
+
+
 def gene_ae(hc_text: bytes, features_text: str, id_separator: str = "_", gw_cutoff: float = 0.9, min_cov: int = 0,
             min_haplo_maf: float = 0.0, ctx: Optional[_lib.Context] = None, threads: int = 8, stats: Optional[dict] = None,
             _pair_counts=None) -> str:
@@ -159,17 +176,7 @@ def gene_ae(hc_text: bytes, features_text: str, id_separator: str = "_", gw_cuto
     counts[single, 1] = np.where(n_used[single] > 0, P.b_count[pr_row[single]], 0)
     multi = np.nonzero(~single)[0]
     if len(multi):
-        items = {"lo": [], "n": [], "run": [], "pair": [], "hap": []}
-        for hap in (0, 1):
-            run0 = P.lab_off[hap][pr_row[multi]]; ln = P.lab_off[hap][pr_row[multi] + 1] - run0
-            nch = (ln + ITEM_LABELS - 1) // ITEM_LABELS
-            owner2, j = _expand(nch)
-            lo2 = run0[owner2] + j * ITEM_LABELS
-            items["lo"].append(lo2); items["n"].append(np.minimum(ITEM_LABELS, run0[owner2] + ln[owner2] - lo2))
-            items["run"].append(run0[owner2]); items["pair"].append(multi[owner2]); items["hap"].append(np.full(len(owner2), hap, dtype=np.uint8))
-        it_lo = np.ascontiguousarray(np.concatenate(items["lo"]), dtype=np.int64); it_n = np.ascontiguousarray(np.concatenate(items["n"]), dtype=np.int32)
-        it_run = np.ascontiguousarray(np.concatenate(items["run"]), dtype=np.int64)
-        it_pair = np.ascontiguousarray(np.concatenate(items["pair"]), dtype=np.int32); it_hap = np.ascontiguousarray(np.concatenate(items["hap"]), dtype=np.uint8)
+        it_lo, it_n, it_run, it_pair, it_hap = work_items(P.lab_off, pr_row[multi], multi)
         w = _lib.phz_gene_work()
         keep = [it_lo, it_n, it_run, it_pair, it_hap, p_begin, p_end]
         vp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
