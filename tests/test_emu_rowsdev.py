@@ -123,19 +123,41 @@ def test_rows_of_a_block_of_150_variants_by_wave_and_by_thread():
         assert outs[0][name] == outs[1][name] == outs[2][name], name
 
 
-@pytest.mark.parametrize("env", [{"PHZ_ROWS_SORT64": "1"}, {"PHZ_ROWS_FAKE_LINE_BITS": "32"}, {"PHZ_ROWS_FAKE_LINE_BITS": "31"}, {"PHZ_ROWS_NO_PRESTAGE": "1"}, {"PHZ_SORT_ONE_LAUNCH": "1"},
-                                 {"PHZ_ROWS_NO_PREKEYS": "1"}],
-                         ids=["sort64", "line_bits_32", "line_bits_31", "no_prestage", "one_launch_sort", "keys_in_the_second_stage"])
+KEY_LAYOUTS = {"sort64": {"PHZ_ROWS_SORT64": "1"}, "line_bits_32": {"PHZ_ROWS_FAKE_LINE_BITS": "32"}, "line_bits_31": {"PHZ_ROWS_FAKE_LINE_BITS": "31"},
+               "no_prestage": {"PHZ_ROWS_NO_PRESTAGE": "1"}, "one_launch_sort": {"PHZ_SORT_ONE_LAUNCH": "1"}, "keys_in_the_second_stage": {"PHZ_ROWS_NO_PREKEYS": "1"}}
+
+
+@pytest.mark.parametrize("env", list(KEY_LAYOUTS.values()), ids=list(KEY_LAYOUTS))
 def test_key_layouts_of_the_ordering_sorts(env, monkeypatch, c1_inputs):
     """The rank order of the variants and the first-appearance order of the covered variants sort 32-bit keys when (line, gap) / (BAM, line) fit and 64-bit
     keys otherwise.  A BAM with more than 2^31 call lines has 32 line bits: a 32-bit (BAM, line) key would shift a 32-bit word by 32 (round-4 advisor
     finding), so that size must take the 64-bit keys; forced here through PHZ_ROWS_FAKE_LINE_BITS on the two-BAM fixture.  Also: the p-value-independent sorts
     enqueued by the first stage (default) or by the second (PHZ_ROWS_NO_PRESTAGE), the first-appearance keys prepared by the first stage (default, the handle knows the
-    tally's shards) or by the second (PHZ_ROWS_NO_PREKEYS), and the one-launch sort passes.  Every variant gives the same bytes."""
+    tally's shards) or by the second (PHZ_ROWS_NO_PREKEYS), and the one-launch sort passes.  Every variant gives the same bytes.
+
+    The one-launch sort runs in a fresh child process (tests/rowsdev_worker.py), on this fixture and on the `ordering` design of tests/rowstage_inputs.py:
+    radix_sort_ranges (phz_sort.h) reads PHZ_SORT_ONE_LAUNCH into a static on its first call in a process, and ctypes.CDLL hands every caller of this process the same
+    loaded library, so once any earlier test has sorted with it, setting the variable here would compare the three-launch sort with itself.  The child has the variable in
+    its environment before it loads the library; the parent, which computes the bytes to compare with, must not have it."""
     lib = emu_library()
     case, gold, load, cfg = next(c for c in _cases() if c[0] == "pipe_two")
     d, vcf_text, bams = _inputs(case, gold, c1_inputs)
     base, _ = run_stages(lib, case, load, cfg, vcf_text, bams)
+    if "PHZ_SORT_ONE_LAUNCH" in env:
+        import subprocess
+        from test_rowstage_limits import DESIGNS, engine_pass, tally_of
+        from phaser_amd import vcf
+        assert "PHZ_SORT_ONE_LAUNCH" not in os.environ
+        r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "rowsdev_worker.py")], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = json.loads(r.stdout.strip().split("\n")[-1])
+        design = DESIGNS["ordering"]
+        ctx = EmuContext(lib)
+        plain, _ = engine_pass(ctx, design, vcf.load_variants(design.vcf_text), tally_of(ctx, design), True, {})
+        for name in OUTPUTS:
+            assert got["pipe_two"][name] == base[name], name
+            assert got["ordering"][name] == plain[name], name
+        return
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     out, eng = run_stages(lib, case, load, cfg, vcf_text, bams)
