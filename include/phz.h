@@ -17,6 +17,8 @@
  *   phz_components       phaser/phaser.py:1861-1882      build_haplotypes / :1985 build_haplotype_v3
  *   phz_variant_links    phaser/phaser.py:1928-1949      generate_hap_network_all (the links of --output_network, :1127-1157)
  *   phz_read_haplotypes  phaser/phaser.py:1086-1123      the read-id lists of --output_read_ids 1, as per-read votes (a, b) for all blocks at once
+ *   phz_haplotag_pick,   (nothing in the reference)      --output_haplotag_bam: one HP / PS tag per template from those votes, and the kept records of an input BAM
+ *   phz_bamdev_haplotag                                  written out again with the tags appended
  *
  * Deliberately NOT exported (SURVEY.md 8(b) suggested them):
  *   phz_load_variants    variant arrays travel with every call instead (6 B per SNP; nothing to keep resident between shards)
@@ -323,6 +325,20 @@ int phz_read_haplotypes(phz_ctx *ctx, int64_t n_blocks, const int64_t *blk_off /
                         const uint8_t *var_skip /* [nv] or NULL */, const uint8_t *bam_skip /* [n_bams] or NULL */,
                         phz_readhap_rec *rows, int64_t rows_cap, int64_t *n_rows, int space);
 
+/* The haplotype tag of every template of ONE BAM, from the records of phz_read_haplotypes (--output_haplotag_bam; DESIGN.md "--output_haplotag_bam, K_tagpick and
+ * K_tagwrite").  rows = those records, in the order phz_read_haplotypes gives them (any order gives the same result); blk_chrom[block] = the chromosome index of a
+ * block of the caller's table, tmpl_base[chrom] = where the chromosome's template ids start in the joint template space (tmpl_base[n_chroms] = its end, at most
+ * n_templates).  Only the rows with bam == `bam` and block < n_phased vote (the blocks behind n_phased are the one-variant blocks of --unphased_vars: they never tag).
+ * Among the voting rows of a template the block with the largest a + b wins, the smallest block index among equal totals; tag[tmpl_base[chrom] + qid] =
+ * (block + 1) << 2 | hp with hp = 1 (a > b: haplotype A), 2 (b > a), 0 (a == b: the winning block tied, and the template does NOT fall through to its next block);
+ * 0 = the template has no vote.  A 64-bit atomic max decides, so every run gives the same words; all n_templates words are written.  n_rows == 0: all zero, no error.
+ * PHZ_E_ARG with a message, the ctx staying usable: a row whose block is outside [0, n_blocks); a blk_chrom outside [0, n_chroms); a qid outside its chromosome's
+ * range; a negative count; n_blocks >= 2^30 (PHZ_HOST arguments are checked before anything is launched and tag is not touched, PHZ_DEVICE ones by the kernel, whose
+ * verdict arrives with the status: tag is then all zero).  All arrays live in `space`. */
+int phz_haplotag_pick(phz_ctx *ctx, const phz_readhap_rec *rows, int64_t n_rows, int64_t n_blocks, int64_t n_phased, int32_t bam,
+                      const int32_t *blk_chrom /* [n_blocks] */, int32_t n_chroms, const int64_t *tmpl_base /* [n_chroms+1] */, int64_t n_templates,
+                      uint32_t *tag /* [n_templates] */, int space);
+
 /* Connected components of the variant graph restricted to edges with keep != 0: label[v] = smallest variant
  * index of v's component.  edge_a == edge_b == NULL: the edge list of the last phz_tally (n_edges must match).
  * Edge arrays handed over in PHZ_HOST space are checked before anything is launched: an endpoint outside [0, nv) is
@@ -367,6 +383,17 @@ const char *phz_bamdev_ref_name(const phz_bamdev *h, int i);
 int64_t phz_bamdev_ref_length(const phz_bamdev *h, int i);
 int phz_bamdev_sizes_of(const phz_bamdev *h, int ref, phz_bamdev_sizes *out);
 int phz_bamdev_pack(phz_bamdev *h, const phz_dev_shard *dst, int n_dst);      /* dst[r] for reference r; entries of empty references are ignored */
+/* The kept records of reference `ref` of an open handle, written out again as BAM records in file order (--output_haplotag_bam): each one byte for byte as in the
+ * inflated stream, except that a record whose template is tagged has HP:C (1 or 2) and PS:I appended, in this order, and its block_size raised by 11.  qid[i] = the
+ * template id of the reference's i-th kept record (the order of phz_bamdev_pack), tag = the n_tag words of phz_haplotag_pick for those ids (a word with hp 0 tags
+ * nothing), blk_ps[block] = the PS value of a block [n_blocks].  qid, tag, blk_ps and out are DEVICE pointers, out_bytes and n_tagged host.
+ * Count, then fill: *out_bytes = the bytes of the records and *n_tagged = the tagged records on every call that gets that far; out == NULL or out_cap < *out_bytes:
+ * PHZ_E_CAPACITY and nothing is written.  A reference without kept records: 0 bytes, no error.
+ * PHZ_E_UNSUPPORTED, naming the offset of the first such record in the inflated stream: a kept record that already carries an HP or a PS field (two of one kind make
+ * an invalid record, and nothing is stripped), or whose aux fields do not end exactly at its block_size.  PHZ_E_ARG: a qid outside [0, n_tag), a tag word that
+ * names no block of blk_ps.  After any of them the handle serves the next call.  Every read of the stream stays inside the record's own block_size. */
+int phz_bamdev_haplotag(phz_bamdev *h, int ref, const int32_t *qid, const uint32_t *tag, int64_t n_tag, const uint32_t *blk_ps, int64_t n_blocks,
+                        uint8_t *out, int64_t out_cap, int64_t *out_bytes, int64_t *n_tagged);
 /* QNAME ids of a device-resident shard, continuing the numbering of earlier BAMs: `store` / `store_off` [n_old + 1] hold the names of
  * ids [0, n_old) in id order (NULL / 0: none yet).  qid[n] = exactly what phz_intern assigns; first_idx[0, *n_new) = record of the
  * first occurrence of every new name, in id order.  All pointers device, n_new host. */

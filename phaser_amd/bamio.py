@@ -129,9 +129,10 @@ def _bgzf_block(data: bytes) -> bytes:
             struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
-def write_bam(path: str, refs: List[Tuple[str, int]], records: List[dict]):
+def write_bam(path: str, refs: List[Tuple[str, int]], records: List[dict], member_bytes: int = 60000):
     """records: dicts with ref_id, pos (1-based), mapq, flag, tlen, qname, cigar [(op_code, len)], seq (text), qual (phred list),
-    tags {"AS": int, ...}."""
+    tags {"AS": int, ...}, aux_raw (bytes appended behind the tags as they are: aux fields of any type).  The stream is cut into BGZF members of
+    member_bytes wherever that falls, inside records too."""
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
     out = bytearray(b"BAM\x01" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(refs)))
     for name, ln in refs:
@@ -147,12 +148,13 @@ def write_bam(path: str, refs: List[Tuple[str, int]], records: List[dict]):
         aux = b""
         for k, v in r.get("tags", {}).items():
             aux += k.encode() + b"i" + struct.pack("<i", v)
+        aux += r.get("aux_raw", b"")
         body = struct.pack("<iiBBHHHiiii", r["ref_id"], r["pos"] - 1, len(qn), r["mapq"], 4680, len(r["cigar"]), r["flag"], l_seq,
                            r["ref_id"], max(0, r.get("mate_pos", r["pos"]) - 1), r["tlen"]) + qn + cg + sb + qb + aux
         out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as f:
-        for i in range(0, len(out), 60000):
-            f.write(_bgzf_block(bytes(out[i:i + 60000])))
+        for i in range(0, len(out), member_bytes):
+            f.write(_bgzf_block(bytes(out[i:i + member_bytes])))
         f.write(_EOF)
 
 
@@ -482,6 +484,139 @@ def shards_from_bam_device(ctx, path: str, interners: Dict[str, "NativeInterner"
         _sys.stderr.write("[phz timing]   bam (device): plan + H2D + inflate + hop %.2f s, allocate + pack %.2f s, other %.2f s, qname ids %.2f s\n"
                           % (t1 - t0, t2 - t1, _t.perf_counter() - t2 - tin, tin))
     return out
+
+
+class PackedBamDevice:
+    """An open handle of the device BAM path AFTER its pack (open_packed_bam_device): the inflated stream and the kept-record list stay in HBM until close().
+    refs = [(reference index, name, kept records, QNAME bytes [cuda uint8], QNAME offsets [cuda int32, n + 1])] of the references that hold kept records, file order."""
+
+    def __init__(self, ctx, lib, h, refs):
+        self.ctx = ctx; self.lib = lib; self.h = h; self.refs = refs
+
+    def qids(self, interners: Dict[str, "NativeInterner"], chrom: str, qnames, qname_off, n: int):
+        """ids (cuda int32) of the records' names from an interner that already knows every one of them: the device store where the names still live there, else the
+        host table.  A name the interner has not seen is an error -- the ids index tables sized before this call."""
+        import ctypes as C
+        it = interners.get(chrom)
+        if it is None:
+            raise ValueError("no QNAME ids for chromosome %s: the run never read a record of it" % chrom)
+        from . import _lib
+        st = it._store
+        if st is not None:                      # a look-up in the device store: phz_intern_device numbers the names, and nothing is appended here
+            P = lambda t: C.c_void_p(t.data_ptr())
+            qid = torch.empty(max(1, n), dtype=torch.int32, device=qnames.device); first = torch.empty(max(1, n), dtype=torch.int32, device=qnames.device)
+            nn = C.c_int64(0)
+            self.ctx.check(self.lib.phz_intern_device(self.ctx.h, P(qnames), P(qname_off), n, P(st["blob"]), P(st["off"]), st["n"], P(qid), P(first), C.byref(nn)))
+            new = int(nn.value); qid = qid[:n]
+        else:                                   # the names are on the host table only (phz_intern has no look-up mode: names it had not seen stay in the table)
+            before = len(it)
+            qn = qnames.cpu().numpy(); qo = qname_off[:n + 1].cpu().numpy()
+            ids = np.zeros(n, dtype=np.int32)
+            self.lib.phz_intern(it.h, C.c_void_p(qn.ctypes.data), C.c_void_p(qo.ctypes.data), n, C.c_void_p(ids.ctypes.data))
+            qid = torch.from_numpy(ids).to(qnames.device)
+            new = len(it) - before
+        if new:
+            raise _lib.PhzError(_lib.PHZ_E_ARG, "chromosome %s: %d QNAMEs that the run had not seen (are these the filters the BAM was read with?)" % (chrom, new))
+        return qid
+
+    def close(self):
+        if self.h is not None:
+            self.lib.phz_bamdev_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def open_packed_bam_device(ctx, path: str, mapq: int, remove_dups: bool, paired_end: bool, isize_cutoff: float = 0.0, chroms=None, device="cuda:0"):
+    """-> (PackedBamDevice, None), or (None, why) when the device path does not take the file.  The same open + pack as shards_from_bam_device with the same filters and
+    chromosomes, so the kept records are the same ones in the same order; the handle stays OPEN (what reads the records again needs the stream: phz_bamdev_haplotag),
+    only the QNAME arrays of the pack are kept, and nothing is interned.  A file beyond the 32-bit offsets of one call is not split here: it is declined."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    f = _lib.phz_bam_filters(int(mapq), 0x2 if paired_end else 0, 0x400 if remove_dups else 0, float(isize_cutoff))
+    h = C.c_void_p()
+    names = [str(c).encode() for c in chroms] if chroms is not None else []
+    arr = (C.c_char_p * max(1, len(names)))(*names) if names else (C.c_char_p * 1)()
+    st = lib.phz_bamdev_open(ctx.h, path.encode(), arr if chroms is not None else None, len(names), C.byref(f), C.byref(h))
+    if st != 0:
+        return None, "status %d: %s" % (st, (lib.phz_last_error(ctx.h) or b"").decode() or lib.phz_strerror(st).decode())
+    try:
+        n_ref = lib.phz_bamdev_n_ref(h)
+        tab = (_lib.phz_dev_shard * max(1, n_ref))()
+        dev = torch.device(device)
+        held = []
+        for i in range(n_ref):
+            sz = _lib.phz_bamdev_sizes()
+            lib.phz_bamdev_sizes_of(h, i, C.byref(sz))
+            n = int(sz.n_reads)
+            if n == 0:
+                continue
+            e = lambda count, dt: torch.empty(max(1, int(count)), dtype=dt, device=dev)
+            t = {"pos": e(n, torch.int32), "cigar_off": e(n + 1, torch.int32), "cigar": e(sz.n_ops, torch.int32), "seq_off": e(n + 1, torch.int32),
+                 "seq2": e(sz.n_seq_bytes, torch.uint8), "qual": e(sz.n_seq_bytes * 4, torch.uint8), "aln_score": e(n, torch.int32),
+                 "has_as": e(n, torch.uint8), "qname_off": e(n + 1, torch.int32), "qnames": e(sz.n_qname_bytes, torch.uint8)}
+            for k, v in t.items():
+                setattr(tab[i], k, v.data_ptr())
+            held.append((i, lib.phz_bamdev_ref_name(h, i).decode(), n, t))
+        st = lib.phz_bamdev_pack(h, tab, n_ref)
+        if st != 0:
+            raise _lib.PhzError(st, "device BAM pack failed: " + lib.phz_last_error(ctx.h).decode())
+        refs = [(i, name, n, t["qnames"], t["qname_off"]) for i, name, n, t in held]
+    except BaseException:
+        lib.phz_bamdev_close(h)
+        raise
+    return PackedBamDevice(ctx, lib, h, refs), None
+
+
+def bam_header_bytes(path: str) -> bytes:
+    """The uncompressed bytes of a BAM in front of its first record (magic, text, reference table), from as many leading BGZF members as they span: nothing
+    behind them is read or inflated."""
+    buf = bytearray()
+    at = None; refs_left = 0          # where the next reference entry starts (None: the fixed part is not complete yet), entries still to come
+    with open(path, "rb") as f:
+        while True:
+            head = f.read(12)
+            if len(head) < 12 or head[:4] != b"\x1f\x8b\x08\x04":
+                raise ValueError("%s: not BGZF, or it ends inside the BAM header" % path)
+            xlen, = struct.unpack_from("<H", head, 10)
+            extra = f.read(xlen)
+            bsize = None; p = 0
+            while p + 4 <= len(extra):
+                slen, = struct.unpack_from("<H", extra, p + 2)
+                if extra[p:p + 2] == b"BC" and slen == 2:
+                    bsize, = struct.unpack_from("<H", extra, p + 4)
+                p += 4 + slen
+            if bsize is None:
+                raise ValueError("%s: a gzip member without the BGZF size field" % path)
+            body = f.read(bsize + 1 - 12 - xlen)
+            if len(extra) < xlen or len(body) < bsize + 1 - 12 - xlen:
+                raise ValueError("%s: it ends inside the BAM header" % path)
+            buf += zlib.decompress(body[:-8], -15)
+            # the walk over the header goes on from where the bytes ran out last time: every field is looked at once, however many members the header spans
+            while True:
+                if at is None:                                   # magic, l_text, text, n_ref
+                    if len(buf) < 8:
+                        break
+                    if buf[:4] != b"BAM\x01":
+                        raise ValueError("%s: not a BAM file" % path)
+                    text_end = 8 + struct.unpack_from("<i", buf, 4)[0]
+                    if len(buf) < text_end + 4:
+                        break
+                    refs_left, = struct.unpack_from("<i", buf, text_end)
+                    at = text_end + 4
+                if refs_left == 0:
+                    return bytes(buf[:at])
+                if len(buf) < at + 4:
+                    break
+                nxt = at + 8 + struct.unpack_from("<i", buf, at)[0]          # l_name, name, l_ref
+                if len(buf) < nxt:
+                    break
+                at = nxt; refs_left -= 1
 
 
 def bam_ref_weights(path: str, threads: int = 0) -> Dict[str, int]:

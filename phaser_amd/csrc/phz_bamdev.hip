@@ -35,12 +35,9 @@
 
 #include "phz.h"
 #include "phz_internal.h"
+#include "phz_bamdev_internal.h"      // struct phz_bamdev, KeptOut, ld16 / ld32 / ldi32
 
 namespace {
-
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-__device__ __forceinline__ int32_t ldi32(const uint8_t *p) { return (int32_t)ld32(p); }
 
 // ------------------------------------------------------------------------------------------------ exclusive scan (uint32), this unit's own
 // out[i] = sum(in[0..i)), out[n] = total.  Three passes at every size: chunk sums, one-block scan of the sums, chunk-local scan + base (16 consecutive elements
@@ -227,10 +224,6 @@ struct SegOut {                 // per segment, written by the counting hop
     uint64_t end_pos;                                      // where the chain arrived (>= the segment's stop)
     uint64_t sq_sum, qn_sum, op_sum;                       // 64-bit sums of base groups, name bytes and 2 x CIGAR ops (upper bound of the
                                                            // normalised op count) over the kept records: the scans below are 32-bit
-};
-
-struct KeptOut {                // kept-record list (structure of arrays)
-    uint64_t *off; int32_t *ref; uint32_t *nops, *sq, *nb, *lqn;
 };
 
 template <int WRITE>
@@ -527,26 +520,11 @@ static void bam_give_back(DevBuf *slot, void *p, size_t cap, bool keep) {
     (void)hipFree(p);
 }
 
-struct phz_bamdev {
-    phz_ctx *ctx = nullptr;
-    bool keep_buffers = true;           // BamKnobs::keep_buffers of the call that opened the handle
-    std::vector<std::pair<std::string, int32_t>> refs;
-    void *d_stream = nullptr;           // inflated bytes of the needed members
-    size_t d_stream_cap = 0;            // its size (the buffer goes back to the ctx's cache when the handle is closed)
-    void *d_work = nullptr;             // kept-record list + offsets (one allocation)
-    size_t d_work_cap = 0;
-    KeptOut K{};
-    int64_t n_kept = 0;
-    uint32_t *co = nullptr, *so = nullptr, *qo = nullptr;      // exclusive prefix sums over the kept list ([n_kept + 1] each)
-    int64_t *d_ref_begin = nullptr;
-    std::vector<int64_t> ref_begin;     // host copy [n_ref + 1]
-    std::vector<uint32_t> h_co, h_so, h_qo;     // values at the reference boundaries
-    std::string err;
-    ~phz_bamdev() {
-        if (d_stream) bam_give_back(ctx ? &ctx->bam_stream : nullptr, d_stream, d_stream_cap, keep_buffers);
-        if (d_work) bam_give_back(ctx ? &ctx->bam_work : nullptr, d_work, d_work_cap, keep_buffers);
-    }
-};
+// (struct phz_bamdev: phz_bamdev_internal.h)
+phz_bamdev::~phz_bamdev() {
+    if (d_stream) bam_give_back(ctx ? &ctx->bam_stream : nullptr, d_stream, d_stream_cap, keep_buffers);
+    if (d_work) bam_give_back(ctx ? &ctx->bam_work : nullptr, d_work, d_work_cap, keep_buffers);
+}
 
 namespace {
 

@@ -57,6 +57,10 @@ enum PhzScratch {
     SC_FISHER_FLAG = 0, SC_FISHER_POS = 1, SC_FISHER_LIST = 2, SC_FISHER_SCAN_TMP = 3,
     // K_match (phz_sample_match): the genotype codes packed 2 bits per donor (the sums stay in registers)
     SC_MATCH_WORDS = 0,
+    // K_tagpick (phz_haplotag_pick): verdict on the rows, best (a + b, block) key per template
+    SC_TAG_FLAG = 0, SC_TAG_BEST = 1,
+    // K_tagsize / K_tagwrite (phz_bamdev_haplotag): verdict + tagged count, output bytes per kept record, their 64-bit exclusive scan, the scan's temporary
+    SC_TAGW_HEAD = 0, SC_TAGW_LEN = 1, SC_TAGW_OFF = 2, SC_TAGW_SCAN_TMP = 3,
     SC_COUNT = 24
 };
 

@@ -559,6 +559,17 @@ class Engine:
         rec = readhap.records(self, _launch=_launch, table=table)
         return {"records": rec, "text": readhap.text(self, rec, table=table), "blocks": table}
 
+    def haplotag(self, bam_index: int, bam_path: str, out_path: str, interners, mapq: int, remove_dups: bool = True, paired_end: bool = True, isize_cutoff: float = 0.0,
+                 threads: int = 0, clock=None) -> dict:
+        """--output_haplotag_bam for one input BAM, after finish(): the records of `bam_path` that pass the filters on this Engine's chromosomes -- they must be the
+        filters the BAM was read with -- written to `out_path` as a BAM with the input's header, every record whose template votes for a haplotype of a phased block
+        carrying HP:C and PS:I (phaser_amd/haplotag.py has the rule).  interners = the {chromosome: NativeInterner} the run's QNAME ids came from; no new name may
+        appear.  -> {"records", "tagged", "bytes", "ms"}, or {"skipped": why} when the device BAM path does not take the file.  The votes come from the read lists the
+        tally left in HBM: the pass must still be the context's resident one.  Needs Config.want_vcf (the per-block arrays).  The host buffer holds the whole output BAM
+        uncompressed.  clock: a haplotag.DeviceClock for a measuring run (tools/haplotag_scale.py); None measures no device call."""
+        from . import haplotag
+        return haplotag.write(self, bam_index, bam_path, out_path, interners, mapq, remove_dups, paired_end, isize_cutoff, threads, clock=clock)
+
     def _fragments(self, noise: float) -> Dict[str, dict]:
         """Stage C for every owned chromosome: C1 = pair tests, pruning, components, ordering keys (numpy / scipy / GPU, the
         heavy parts once over all chromosomes); C2 = block phasing + row text, all chromosomes through ONE native thread pool."""

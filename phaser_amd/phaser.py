@@ -6,7 +6,8 @@ BED and VCF are read in-process) and the seven multiprocessing stages are one `E
 The phased VCF (`write_vcf`) is written as BGZF `<o>.vcf.gz` with its tabix index `<o>.vcf.gz.tbi`.  `--output_network VARIANT`
 writes `<o>.network.links.txt` / `<o>.network.nodes.txt` for the block that holds the variant (phaser_amd/network.py).  `--output_read_haplotypes 1`
 (not an option of the reference) writes `<o>.read_haplotypes.txt`: per (block, BAM, read) its call lines on haplotype A's alleles and on the other ones
-(phaser_amd/readhap.py).  Not supported: `--process_slow`.
+(phaser_amd/readhap.py).  `--output_haplotag_bam 1` (not an option of the reference either) writes `<o>.haplotag.<k>.bam` for the k-th input BAM: the records that passed the
+filters, tagged HP / PS with the haplotype their template votes for (phaser_amd/haplotag.py).  Not supported: `--process_slow`.
 
     python -m phaser_amd.phaser --vcf S.vcf.gz --bam a.bam,b.bam --sample S1 --mapq 255 --baseq 10 --paired_end 1 --o out
 
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import bamio, samio, vcf
+from . import _lib, bamio, samio, vcf
 from . import dist as pdist
 from .engine import Config, Engine, binom_cdf_dedup
 
@@ -89,6 +90,11 @@ def build_parser():
     p.add_argument("--output_read_haplotypes", type=int, default=0,
                    help="1: also write <o>.read_haplotypes.txt -- per (block, BAM, read) the number of its call lines on haplotype A's alleles and on the other "
                         "ones, and the haplotype they vote for (not an option of the reference; one rank only)")
+    p.add_argument("--output_haplotag_bam", type=int, default=0,
+                   help="1: also write <o>.haplotag.<k>.bam for the k-th input BAM -- the records that passed --mapq / --paired_end / --remove_dups / --isize on the "
+                        "chromosomes of the run, each tagged HP:C (1 = haplotype A, 2 = the other one) and PS:I (the block's start) when its template votes for a "
+                        "haplotype of a phased block (not an option of the reference; one rank only, BAM inputs only; the whole output BAM is held uncompressed in "
+                        "host memory)")
     p.add_argument("--process_slow", type=int, default=0, required=False)
     return p
 
@@ -117,6 +123,10 @@ def check_args(args, world):
         fatal_error("--py_hash_order 1 needs all chromosomes on one rank (run it without torch.distributed).")
     if args.output_read_haplotypes and world > 1:
         fatal_error("--output_read_haplotypes 1 needs all chromosomes on one rank (run it without torch.distributed).")
+    if args.output_haplotag_bam and world > 1:
+        fatal_error("--output_haplotag_bam 1 needs all chromosomes on one rank (run it without torch.distributed).")
+    if args.output_haplotag_bam and any(b.endswith(".sam") for b in args.bam.split(",")):
+        fatal_error("--output_haplotag_bam 1 needs BAM inputs (a .sam input has no records to copy).")
     if not os.path.isfile(args.vcf):
         fatal_error("VCF file does not exist.")
     for xfile in [args.blacklist, args.haplo_count_blacklist] + args.bam.split(","):
@@ -269,6 +279,8 @@ class _Run:
         self.pool_threads = max(0, args.threads if args.threads > 1 else 0)          # 0: the library's default
         self.vs = self.eng = self.mine = None          # set by load_variant_table / make_engine
         self.interners: Dict[str, object] = {}
+        self.haplotag_clock = None     # a measuring caller (tools/haplotag_scale.py) sets haplotag.DeviceClock: ctx -> the clock of one file's device calls
+        self.haplotag_results = []     # what Engine.haplotag returned for every BAM that got that far (write_haplotag_bams)
         self.bam_paths = []            # which decoder read each BAM: "device" (phz_bamdev_*), "host" (phz_bam_*: the file was declined or PHZ_BAM_HOST=1), "sam" (text)
 
     @property
@@ -446,7 +458,7 @@ def make_engine(run):
                  id_separator=args.id_separator, unphased_vars=args.unphased_vars, gw_phase_method=args.gw_phase_method,
                  output_read_ids=args.output_read_ids, unique_ids=args.unique_ids, haplo_count_bam_exclude=excl, py_hash_order=args.py_hash_order,
                  include_indels=args.include_indels, host_threads=run.threads)
-    if args.output_network != "" or args.output_read_haplotypes == 1:
+    if args.output_network != "" or args.output_read_haplotypes == 1 or args.output_haplotag_bam == 1:
         cfg.want_vcf = True            # the per-block arrays (the switch write_vcf and --py_hash_order set): the block of the variant is looked up in them
     mapper0 = None
     if run.ctx_task is not None:
@@ -571,6 +583,30 @@ def write_read_haplotypes(run):
     run.clock.mark("read haplotypes")
 
 
+def write_haplotag_bams(run, bams):
+    """--output_haplotag_bam: every input BAM again through the device BAM path with its own filters, its kept records rewritten with HP / PS on the GPU
+    (phaser_amd/haplotag.py).  A BAM that the host decoder read is skipped with a line that says so."""
+    args, say = run.args, run.say
+    for bi, (bam, mq, isz, pe) in enumerate(bams):
+        path = "%s.haplotag.%d.bam" % (args.o, bi + 1)
+        if run.bam_paths[bi] != "device":
+            say("     no haplotagged BAM for %s: the %s decoder read it, and the records are rewritten from the device BAM path's stream" % (bam, run.bam_paths[bi]))
+            continue
+        try:
+            res = run.eng.haplotag(bi, bam, path, run.interners, int(mq), args.remove_dups == 1, int(pe) == 1, isz, threads=run.pool_threads,
+                                   clock=run.haplotag_clock(run.eng.ctx) if run.haplotag_clock else None)
+        except _lib.PhzError as e:          # a file the record rewrite refuses (it already carries HP / PS): the other outputs are still written
+            if e.status != _lib.PHZ_E_UNSUPPORTED:
+                raise
+            res = {"skipped": str(e)}
+        if "skipped" in res:
+            say("     no haplotagged BAM for %s: %s" % (bam, res["skipped"]))
+        else:
+            say("     %d records written to %s, %d of them tagged HP / PS" % (res["records"], path, res["tagged"]))
+        run.haplotag_results.append(res)
+    run.clock.mark("haplotagged BAMs")
+
+
 def write_outputs(run, files, data, sample_col):
     """The five files and, with --write_vcf 1, the phased VCF -> (genome-wide phased, phase corrected) counts of the VCF."""
     args, say = run.args, run.say
@@ -660,6 +696,8 @@ def _main(run):
         write_network(run)
     if args.output_read_haplotypes == 1:
         write_read_haplotypes(run)
+    if args.output_haplotag_bam == 1:
+        write_haplotag_bams(run, bams)
     if files is not None:
         for line in run.eng.log[n_before:]:
             say(line)
